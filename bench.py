@@ -13,6 +13,10 @@ frames per second over the whole job.  Workloads:
       identical shapes on every rank, different seeds -- the default at --gpus N > 1 (and a `c3` leg of the N = 1 line,
       through the data-parallel exchange path on a 1-rank RCCL group).
 --mode decode benchmarks the autoregressive loop instead.  One JSON line is printed by rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else the line can carry:
+the packer-extreme batches, the per-kernel roofline pass, the CPU baseline, the data-parallel legs and the decode / finetune /
+fp32 / exchange-path / c3 / drop-in sub-benchmarks.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import ctypes as C
@@ -105,10 +109,33 @@ def load_kernel_stats(suffix="train_bf16_kernel_stats.csv"):
     return names[-1], steps[0], {r["Name"]: (int(r["Calls"]) / steps[0], float(r["AverageNs"])) for r in rows}
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def write_outputs(dirname, arrays):
+    """{name: array} -> dirname/<name>.npy in float32 (64 MB at most in all)."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, "outputs to dump: %d bytes, limit %d" % (total, DUMP_LIMIT_BYTES)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
+def train_outputs(model, vals):
+    """What a caller of the timed training step has after the last step: the loss values the step returned and the model's updated
+    state (every floating-point tensor of state_dict(), in its order, flattened: a fixed sample of 4 M values when larger)."""
+    from bench_decode import sample_flat
+    losses = vals if torch.is_tensor(vals) else torch.stack([torch.as_tensor(v).reshape(()) for v in vals])
+    state = torch.cat([t.detach().reshape(-1).float() for t in model.state_dict().values() if t.is_floating_point()])
+    return {"losses": losses.detach().float().cpu().numpy(), "state_sample": sample_flat(state, 4 << 20, seed=0)}
+
+
 def _sub_bench(extra, env=None):
-    """Run another bench mode in a child process and return the fields of its JSON line that matter on the parent's line."""
+    """Run another bench mode in a child process (with --full: as it ran inside the full line) and return the fields of its JSON line that
+    matter on the parent's line."""
     import subprocess
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "1"] + extra, capture_output=True, text=True, timeout=900,
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full"] + extra, capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, **env) if env else None)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     if r.returncode != 0 or not lines:
@@ -143,6 +170,11 @@ def main():
     ap.add_argument("--no-roofline-pass", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
                     help="train mode, 1 GPU: skip the decode / finetune / fp32_mode sub-benchmarks added to the JSON line")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, run everything else the JSON line can carry: packer extremes, roofline pass, CPU baseline, "
+                         "data-parallel legs, sub-benchmarks (the --no-* switches above trim this); without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, <= 64 MB)")
     args = ap.parse_args()
     if args.workload is None:
         args.workload = "c3" if (args.gpus > 1 and args.mode == "train") else "lj"
@@ -180,7 +212,7 @@ def main():
 
     if args.mode == "decode":
         from bench_decode import run_decode
-        return run_decode(args, rank, world, device)
+        return run_decode(args, rank, world, device, dump=lambda arrays: write_outputs(args.dump_outputs, arrays))
 
     from hyperparams import hparams as hp
     from transformer.tacotron import Tacotron, initialize_variables
@@ -266,10 +298,12 @@ def main():
     vals, elapsed, host_s, dev_ms = timed(batches, args.steps, args.warmup)
     loss = float(vals[0])
     assert np.isfinite(loss), "training diverged: loss = %r" % loss
+    if args.dump_outputs and rank == 0:                 # (before anything below steps the model again)
+        write_outputs(args.dump_outputs, train_outputs(model, vals))
     # the two extremes of the reference's packer (dataloader.py:401-410: <= 8000 frames and B (S^2 + T^2) <= 7e6 per batch) next to the
     # typical batch: same model, same step, a few steps each
     extremes = {}
-    if world == 1 and args.mode == "train" and args.workload == "lj" and (B, S, T) == (14, 114, 582) and not args.no_extras:
+    if args.full and world == 1 and args.mode == "train" and args.workload == "lj" and (B, S, T) == (14, 114, 582) and not args.no_extras:
         for (b_, s_, t_) in ((32, 50, 250), (9, 158, 808)):
             _, el, _, _ = timed([make_batch(cfg, b_, s_, t_, seed=7, device=device)], max(5, args.steps // 2), 2)
             n_ = max(5, args.steps // 2)
@@ -309,7 +343,7 @@ def main():
                                 "frac": round(ach / peak, 4), "flops_per_step": step_flops}
         if extremes:
             out["packer_extremes"] = extremes
-    if rank == 0 and world == 1 and not args.no_roofline_pass and not dropin and trainer is not None:
+    if args.full and rank == 0 and world == 1 and not args.no_roofline_pass and not dropin and trainer is not None:
         # dominant kernel (MFMA GEMM): per-launch HIP events on the launch stream, same steps, separate pass
         lib = L.load()
         lib.b2s_prof_enable(1)
@@ -431,7 +465,7 @@ def main():
                                    "second stream concurrently with the rest of the backward pass, so their event durations -- and those "
                                    "of the main-stream kernels they overlap -- include time spent sharing the CUs; <true, true, *> "
                                    "durations also include the split-K slab reduction that belongs to the launch"}
-    if (world > 1 or force_dp) and args.mode == "train" and not args.no_extras:
+    if args.full and (world > 1 or force_dp) and args.mode == "train" and not args.no_extras:
         # One invocation decides the data-parallel defaults: after the headline leg (bucketed all-reduce, the wire named in config.grad_payload) the same
         # step is timed with the other gradient wire, with the sharded optimizer (reduce-scatter + all-gather of the updated parameters) on both
         # wires, with the whole exchange path on but the wire removed (every collective completes at once: what the rank pays for hooks, packs,
@@ -497,13 +531,13 @@ def main():
             best = min((l for l in legs if l.get("ms_per_step") and l["dp_mode"] and "wire removed" not in l["leg"]), key=lambda l: l["ms_per_step"])
             out["fastest_dp_leg"] = {"leg": best["leg"], "ms_per_step": best["ms_per_step"]}
         trainer = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_train()
     if world > 1 or force_dp:
         out_n = torch.distributed.get_world_size()
         if rank == 0:
             out["rccl_ranks"] = out_n                  # what the RCCL group itself reports (== n_gpus)
-    if rank == 0 and world == 1 and not force_dp and args.mode == "train" and args.dtype == "bf16" and args.workload == "lj" and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not force_dp and args.mode == "train" and args.dtype == "bf16" and args.workload == "lj" and not args.no_extras:
         # the other BASELINE.json configs on the same JSON line (each in its own process: the hparams object is global):
         #   decode     configs[3]  64 utterances x 1000 frames, hipGraph-captured KV-cached loop
         #   finetune   configs[4]  frozen encoder + guided-attention loss, batches from a 30-utterance pool

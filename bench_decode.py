@@ -44,6 +44,16 @@ def load_pmc(suffix):
     return names[-1], "unrecorded (round-2 file)", d
 
 
+def sample_flat(x, n, seed):
+    """Flattened tensor -> float32 NumPy array: all of it when it has at most n elements, else n elements at sorted indices drawn from a
+    generator seeded with `seed` (the same indices for the same size on every run)."""
+    x = x.detach().reshape(-1)
+    if x.numel() > n:
+        idx = np.sort(np.random.default_rng(seed).integers(0, x.numel(), size=n))
+        x = x[torch.from_numpy(idx).to(x.device)]
+    return x.float().cpu().numpy()
+
+
 def decode_bytes_per_step(B, S, t, e, Dd=768, Ld=6, weights=49.9e6):
     """weights once + self-KV read + cross-KV read + KV append."""
     return weights * e + Ld * 2 * B * Dd * e * (t + S + 1)
@@ -67,7 +77,8 @@ def cpu_baseline_decode(frames=60, B=8, S=100):
                       "per frame, so 64x1000 is not run on the CPU" % (B, S, frames), "seconds": round(dt, 2)}
 
 
-def run_decode(args, rank, world, device):
+def run_decode(args, rank, world, device, dump=None):
+    """dump: called on rank 0 with {name: array} of what the last timed job returned when args.dump_outputs is set."""
     from hyperparams import hparams as hp
     from transformer.tacotron import Tacotron, initialize_variables
     import synthesize
@@ -106,21 +117,27 @@ def run_decode(args, rank, world, device):
         torch.distributed.barrier()
     elapsed = time.perf_counter() - t0
     assert bool(torch.isfinite(r["mel_aft"]).all())
-    # the same job with the reference's return contract (NumPy arrays on the host: + a 2 GB device-to-host copy of the alignments)
-    r = None
-    r = synthesize.eval_batch(model, batch, use_bar=False, bar_interval=-1, sync_interval=64)       # (untimed: pins the host staging buffers)
-    r = None
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(reps):                              # same number of repetitions as the device-resident figure
+    if args.dump_outputs and rank == 0 and dump is not None:
+        dump({"mel_pre": r["mel_pre"].float().cpu().numpy(), "mel_aft": r["mel_aft"].float().cpu().numpy(),
+              "generated_lengths": r["generated_lengths"].float().cpu().numpy(),
+              "encdec_alignments_sample": sample_flat(torch.cat([a.reshape(-1) for a in r["alignments"]["encdec"]]), 1 << 20, seed=0)})
+    host_elapsed = None
+    if args.full:
+        # the same job with the reference's return contract (NumPy arrays on the host: + a 2 GB device-to-host copy of the alignments)
         r = None
-        r = synthesize.eval_batch(model, batch, use_bar=False, bar_interval=-1, sync_interval=64)
-    host_elapsed = (time.perf_counter() - t1) / reps
+        r = synthesize.eval_batch(model, batch, use_bar=False, bar_interval=-1, sync_interval=64)       # (untimed: pins the host staging buffers)
+        r = None
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(reps):                              # same number of repetitions as the device-resident figure
+            r = None
+            r = synthesize.eval_batch(model, batch, use_bar=False, bar_interval=-1, sync_interval=64)
+        host_elapsed = (time.perf_counter() - t1) / reps
+        assert np.isfinite(r["mel_aft"]).all()
     if world > 1:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
-    assert np.isfinite(r["mel_aft"]).all()
     if rank == 0:
         e = 2 if args.dtype == "bf16" else 4
         step_ms = elapsed / reps / frames * 1e3
@@ -143,14 +160,14 @@ def run_decode(args, rank, world, device):
                "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
                "config": {"workload": "eval_batch: %d utterances x %d frames, S=%d, stop bias -100, decoder dropout on, default hparams"
                                       % (B, frames, S), "parallelism": "replicas x%d" % world},
-               "value_incl_host_copy": round(B * frames / host_elapsed, 1),      # the reference's return contract (synthesize.py:57-61: NumPy)
-               "ms_per_step_incl_host_copy": round(host_elapsed / frames * 1e3, 4),
+               "value_incl_host_copy": round(B * frames / host_elapsed, 1) if host_elapsed else None,      # the reference's return contract (synthesize.py:57-61: NumPy)
+               "ms_per_step_incl_host_copy": round(host_elapsed / frames * 1e3, 4) if host_elapsed else None,
                "roofline": {"bound": "hbm", "achieved": round(ach, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
                             "frac": round(ach / PEAK_HBM_GBS, 4), "traffic": traffic, "traffic_unit": "bytes per frame (HBM side, PMC)", "traffic_source": traffic_source,
                             "bytes_per_step_avg": avg_bytes,
                             "note": "algorithmic bytes per frame step (weights + KV) / wall time per frame incl. encoder and postnet; results "
                                     "(mels, lengths, alignments) complete in HBM -- value_incl_host_copy adds the reference's NumPy return (PCIe)"}}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_decode()
     if world > 1:
         torch.distributed.destroy_process_group()

@@ -137,7 +137,7 @@ def test_rccl_exchange_path_single_rank():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
            "--no-roofline-pass", "--batch", "4", "--S", "40", "--T", "120"]
     outs = []
     for force in (True, False):

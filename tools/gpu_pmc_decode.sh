@@ -7,7 +7,7 @@ out=$repo/gpurun_out
 export TMPDIR=/tmp
 cd /tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out/${tag}_$c -o p -- python $repo/bench.py --mode decode --steps 10 --warmup 1 --no-cpu-baseline > $out/${tag}_$c.log 2>&1
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out/${tag}_$c -o p -- python $repo/bench.py --full --mode decode --steps 10 --warmup 1 --no-cpu-baseline > $out/${tag}_$c.log 2>&1
   rm -f $out/${tag}_$c/*kernel_trace.csv
 done
 cd $repo

@@ -4,10 +4,10 @@
 tag=${1:-r03}
 repo=$PWD; out=$repo/gpurun_out; mkdir -p $out
 export TMPDIR=/tmp
-python bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err; tail -c 300 $out/${tag}_bench.json
+python bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err; tail -c 300 $out/${tag}_bench.json
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_prof_train -o train -- python $repo/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-roofline-pass --no-extras > $out/${tag}_prof_train.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_prof_decode -o decode -- python $repo/bench.py --mode decode --no-cpu-baseline > $out/${tag}_prof_decode.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_prof_decode -o decode -- python $repo/bench.py --full --mode decode --no-cpu-baseline > $out/${tag}_prof_decode.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_prof_ln -o ln -- python $repo/tools/ln_rate.py > $out/${tag}_prof_ln.log 2>&1
 cd $repo
 python tools/timeline.py $(find $out/${tag}_prof_train -name "*kernel_trace.csv" | head -1) --list > $out/${tag}_train_timeline.txt 2>&1
