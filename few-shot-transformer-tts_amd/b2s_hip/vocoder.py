@@ -1,0 +1,246 @@
+"""ctypes binding of libb2s_vocoder.so (C ABI in include/b2s_vocoder.h): batched Griffin-Lim vocoder and mel front end on the GPU.
+
+The reference's utils/audio.py surface (mel2wav, get_spectrograms, save_wav) with librosa 0.6.0 semantics, run as HIP kernels for
+gfx950.  There is no CPU fallback: CPU tensors are refused and a missing library is an error.  Only n_fft 2048, win_length 800,
+hop_length 200 and 80 mels are compiled in; other values are refused by the library with a message naming the supported set.
+"""
+import ctypes as C
+import os
+import wave
+
+import numpy as np
+import torch
+
+from .lib import B2SError, ptr
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(os.path.dirname(_HERE), "libb2s_vocoder.so")
+
+WS_MEL2WAV, WS_WAV2MEL = 0, 1
+
+
+class Params(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("sr", "n_fft", "hop", "win", "n_mels")] + \
+               [(n, C.c_float) for n in ("preemphasis", "ref_db", "max_db", "max_abs_value", "power")] + \
+               [("symmetric_mel", C.c_int32)]
+
+
+P = C.c_void_p
+_PROTOS = {
+    "b2s_voc_version": (C.c_int, []),
+    "b2s_voc_last_error": (C.c_char_p, []),
+    "b2s_voc_ws_bytes": (C.c_size_t, [C.POINTER(Params), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "b2s_voc_mel2wav": (C.c_int, [C.POINTER(Params), P, P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, C.c_size_t, P]),
+    "b2s_voc_wav2mel": (C.c_int, [C.POINTER(Params), P, P, P, C.c_int, C.c_int, C.c_int, P, P, P, C.c_size_t, P]),
+}
+EXPORTS = sorted(_PROTOS)
+
+_lib = None
+
+
+def load():
+    """Load libb2s_vocoder.so (raises B2SError if it is missing -- there is no fallback path)."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise B2SError("libb2s_vocoder.so not found at %s -- build it with few-shot-transformer-tts_amd/csrc/build.sh "
+                       "(or __graft_entry__.build()); there is no CPU fallback" % LIB_PATH)
+    lib = C.CDLL(LIB_PATH)
+    for name, (res, args) in _PROTOS.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _lib = lib
+    return lib
+
+
+def check(rc):
+    if rc != 0:
+        raise B2SError(load().b2s_voc_last_error().decode("utf-8", "replace"))
+
+
+def _hp(hp=None):
+    if hp is None:
+        from hyperparams import hparams as hp
+    return hp
+
+
+def params(hp=None):
+    hp = _hp(hp)
+    return Params(sr=int(hp.sr), n_fft=int(hp.n_fft), hop=int(hp.hop_length), win=int(hp.win_length), n_mels=int(hp.num_mels),
+                  preemphasis=float(hp.preemphasis), ref_db=float(hp.ref_db), max_db=float(hp.max_db),
+                  max_abs_value=float(hp.max_abs_value), power=float(hp.power), symmetric_mel=int(bool(hp.symmetric_mel)))
+
+
+# ---------------------------------------------------------------------------------------------------------------- mel basis (host)
+
+def _hz_to_mel(f):
+    f = np.asanyarray(f, dtype=np.float64)
+    f_sp, min_log_hz, logstep = 200.0 / 3, 1000.0, np.log(6.4) / 27.0
+    return np.where(f >= min_log_hz, min_log_hz / f_sp + np.log(np.maximum(f, min_log_hz) / min_log_hz) / logstep, f / f_sp)
+
+
+def _mel_to_hz(m):
+    m = np.asanyarray(m, dtype=np.float64)
+    f_sp, min_log_hz, logstep = 200.0 / 3, 1000.0, np.log(6.4) / 27.0
+    min_log_mel = min_log_hz / f_sp
+    return np.where(m >= min_log_mel, min_log_hz * np.exp(logstep * (m - min_log_mel)), f_sp * m)
+
+
+_basis_cache = {}
+
+
+def mel_basis(hp=None):
+    """librosa.filters.mel(sr, n_fft, n_mels) (Slaney scale, htk=False, norm=1): [n_mels, 1 + n_fft // 2] float64, cached."""
+    hp = _hp(hp)
+    key = ("basis", int(hp.sr), int(hp.n_fft), int(hp.num_mels))
+    if key not in _basis_cache:
+        sr, n_fft, n_mels = key[1:]
+        fftfreqs = np.linspace(0, sr / 2.0, 1 + n_fft // 2)
+        mel_f = _mel_to_hz(np.linspace(_hz_to_mel(0.0), _hz_to_mel(sr / 2.0), n_mels + 2))
+        fdiff = np.diff(mel_f)
+        ramps = mel_f[:, None] - fftfreqs[None, :]
+        w = np.maximum(0.0, np.minimum(-ramps[:-2] / fdiff[:-1, None], ramps[2:] / fdiff[1:, None]))
+        w *= (2.0 / (mel_f[2:n_mels + 2] - mel_f[:n_mels]))[:, None]
+        w.flags.writeable = False
+        _basis_cache[key] = w
+    return _basis_cache[key]
+
+
+def inverse_mel_basis(hp=None):
+    """np.linalg.pinv(mel_basis): [1 + n_fft // 2, n_mels] float64, cached (the reference's mel_to_linear)."""
+    hp = _hp(hp)
+    key = ("pinv", int(hp.sr), int(hp.n_fft), int(hp.num_mels))
+    if key not in _basis_cache:
+        inv = np.linalg.pinv(mel_basis(hp))
+        inv.flags.writeable = False
+        _basis_cache[key] = inv
+    return _basis_cache[key]
+
+
+def _device_tables(hp, device):
+    """(basis [n_mels, n_bins], pinv^T [n_mels, n_bins]) as fp32 on `device`, uploaded once per device."""
+    key = ("dev", int(hp.sr), int(hp.n_fft), int(hp.num_mels), str(device))
+    if key not in _basis_cache:
+        basis = torch.from_numpy(np.ascontiguousarray(mel_basis(hp), dtype=np.float32)).to(device)
+        inv_t = torch.from_numpy(np.ascontiguousarray(inverse_mel_basis(hp).T, dtype=np.float32)).to(device)
+        _basis_cache[key] = (basis, inv_t)
+    return _basis_cache[key]
+
+
+# ------------------------------------------------------------------------------------------------------------------- batched calls
+
+def _offsets(frames, device):
+    off = np.zeros(len(frames) + 1, dtype=np.int32)
+    np.cumsum(frames, out=off[1:])
+    return off, torch.from_numpy(off).to(device)
+
+
+def _workspace(lib, prm, B, total, max_frames, which, device):
+    nbytes = lib.b2s_voc_ws_bytes(C.byref(prm), B, total, max_frames, which)
+    if nbytes == 0:
+        check(1)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def mel2wav_batch(mels, lengths, n_iter=None, hp=None):
+    """Vocode a padded batch of normalised mels [B, Tmax, n_mels] (cuda tensor or NumPy) with per-utterance frame counts `lengths`
+    (host sequence, every T_b >= 2).  Returns (wav [B, hop * (Tmax - 1)] cuda fp32, zero past each hop * (T_b - 1), wav_lengths).
+    Runs on torch.cuda.current_stream() without synchronising; the workspace comes from the torch allocator."""
+    hp = _hp(hp)
+    lib = load()
+    n_iter = int(hp.n_iter if n_iter is None else n_iter)
+    if isinstance(mels, np.ndarray):
+        mels = torch.from_numpy(np.ascontiguousarray(mels, dtype=np.float32)).cuda()
+    if mels.dim() != 3:
+        raise B2SError("mels must be [B, Tmax, n_mels], got %s" % (tuple(mels.shape),))
+    if mels.dtype != torch.float32:
+        raise B2SError("mels must be float32, got %s" % mels.dtype)
+    ptr(mels)                                          # refuses CPU / non-contiguous tensors before anything is uploaded
+    B, Tmax = int(mels.shape[0]), int(mels.shape[1])
+    frames = [int(t) for t in lengths]
+    if len(frames) != B:
+        raise B2SError("%d lengths for a batch of %d" % (len(frames), B))
+    if any(t < 2 or t > Tmax for t in frames):
+        raise B2SError("every length must be in 2..Tmax=%d (got %s); T = 1 gives an empty waveform" % (Tmax, frames))
+    prm = params(hp)
+    device = mels.device
+    off_h, off = _offsets(frames, device)
+    total = int(off_h[-1])
+    ws = _workspace(lib, prm, B, total, Tmax, WS_MEL2WAV, device)
+    _, inv_t = _device_tables(hp, device)
+    wav = torch.empty(B, int(hp.hop_length) * (Tmax - 1), dtype=torch.float32, device=device)
+    check(lib.b2s_voc_mel2wav(C.byref(prm), ptr(mels), ptr(off), B, Tmax, total, n_iter, ptr(inv_t), ptr(wav), ptr(ws),
+                              ws.numel(), torch.cuda.current_stream(device).cuda_stream))
+    return wav, [int(hp.hop_length) * (t - 1) for t in frames]
+
+
+def wav2mel_batch(wavs, lengths, hp=None):
+    """Normalised mels of a padded batch of waveforms [B, Lmax] (cuda tensor or NumPy) with per-utterance sample counts `lengths`
+    (host sequence, every L_b >= 2).  Returns (mels [B, 1 + Lmax // hop, n_mels] cuda fp32, zero past each frame count,
+    frame_lengths = 1 + L_b // hop)."""
+    hp = _hp(hp)
+    lib = load()
+    if isinstance(wavs, np.ndarray):
+        wavs = torch.from_numpy(np.ascontiguousarray(wavs, dtype=np.float32)).cuda()
+    if wavs.dim() != 2:
+        raise B2SError("wavs must be [B, Lmax], got %s" % (tuple(wavs.shape),))
+    if wavs.dtype != torch.float32:
+        raise B2SError("wavs must be float32, got %s" % wavs.dtype)
+    ptr(wavs)
+    B, Lmax = int(wavs.shape[0]), int(wavs.shape[1])
+    samples = [int(n) for n in lengths]
+    if len(samples) != B:
+        raise B2SError("%d lengths for a batch of %d" % (len(samples), B))
+    if any(n < 2 or n > Lmax for n in samples):
+        raise B2SError("every length must be in 2..Lmax=%d samples (got %s)" % (Lmax, samples))
+    prm = params(hp)
+    hop = int(hp.hop_length)
+    device = wavs.device
+    frames = [1 + n // hop for n in samples]
+    off_h, off = _offsets(frames, device)
+    total = int(off_h[-1])
+    Tout = 1 + Lmax // hop
+    ws = _workspace(lib, prm, B, total, Tout, WS_WAV2MEL, device)
+    basis, _ = _device_tables(hp, device)
+    lens = torch.tensor(samples, dtype=torch.int32).to(device)
+    mels = torch.zeros(B, Tout, int(hp.num_mels), dtype=torch.float32, device=device)
+    check(lib.b2s_voc_wav2mel(C.byref(prm), ptr(wavs), ptr(lens), ptr(off), B, Lmax, total, ptr(basis), ptr(mels), ptr(ws),
+                              ws.numel(), torch.cuda.current_stream(device).cuda_stream))
+    return mels, frames
+
+
+# ------------------------------------------------------------------------------------------------------ the reference's signatures
+
+def mel2wav(mel, hp=None):
+    """The reference's utils.audio.mel2wav: normalised mel [T, n_mels] (NumPy) -> float32 wav of hop * (T - 1) samples."""
+    mel = np.asarray(mel, dtype=np.float32)
+    if mel.ndim != 2:
+        raise B2SError("mel must be [T, n_mels], got %s" % (mel.shape,))
+    wav, lens = mel2wav_batch(mel[None], [mel.shape[0]], hp=hp)
+    return wav[0, :lens[0]].cpu().numpy()
+
+
+def get_spectrograms(wav, hp=None):
+    """The reference's utils.audio.get_spectrograms: waveform (NumPy) -> normalised mel [1 + len // hop, n_mels] float32."""
+    wav = np.asarray(wav, dtype=np.float32)
+    if wav.ndim != 1:
+        raise B2SError("wav must be 1-D, got %s" % (wav.shape,))
+    mels, frames = wav2mel_batch(wav[None], [wav.shape[0]], hp=hp)
+    return mels[0, :frames[0]].cpu().numpy()
+
+
+def save_wav(wav, path, hp=None):
+    """The reference's save_wav: peak-normalise by 1 / max(0.01, max|wav|) and write 16-bit PCM mono at hp.sr (what soundfile
+    writes for .wav by default), through the stdlib `wave` module."""
+    hp = _hp(hp)
+    wav = np.asarray(wav, dtype=np.float64).reshape(-1)
+    scaled = wav / max(0.01, float(np.max(np.abs(wav))) if wav.size else 0.0)
+    pcm = np.round(np.clip(scaled, -1.0, 1.0) * 32767).astype("<i2")
+    with wave.open(path, "wb") as w:
+        w.setnchannels(1)
+        w.setsampwidth(2)
+        w.setframerate(int(hp.sr))
+        w.writeframes(pcm.tobytes())
+    return path

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Build libb2s_hip.so for gfx950 (MI355X).  hipcc cross-compiles without a GPU.
+# Build libb2s_hip.so and libb2s_vocoder.so for gfx950 (MI355X).  hipcc cross-compiles without a GPU.
 #   build.sh            only what changed
 #   build.sh --clean    recompile every source (what __graft_entry__.build() runs)
 #   build.sh --lab      measurement build with -DB2S_LAB (B2S_LAB_* environment switches that change results: skip the encoder, drop the
@@ -24,3 +24,11 @@ for p in "${pids[@]}"; do wait $p; done
 objs=""; for f in $SRCS; do objs="$objs $OBJ/$f.o"; done
 hipcc --offload-arch=gfx950 -shared -fPIC $objs -o $OUT
 echo "built $OUT"
+# the vocoder / mel front end is a library of its own (include/b2s_vocoder.h); not part of the measurement build
+if [ "$1" != "--lab" ]; then
+  VOUT=../libb2s_vocoder.so
+  if [ "$1" = "--clean" ] || [ ! -f $VOUT ] || [ vocoder/vocoder.hip -nt $VOUT ] || [ ../../include/b2s_vocoder.h -nt $VOUT ]; then
+    hipcc $FLAGS -shared vocoder/vocoder.hip -o $VOUT
+  fi
+  echo "built $VOUT"
+fi

@@ -235,7 +235,11 @@ def save_eval_results(names, mel_pre, mel_aft, alignments, input_lengths, genera
     `<name>.npy` = mel_aft[i][:generated_lengths[i]] always; `<name>.wav` (+ `<name>_trim.wav`), `<name>_mel.png` and
     `<name>_align.png` when the reference's vocoder / plotting helpers (`utils.audio`, `utils.infolog`: out of this
     package's scope) are importable, i.e. when a reference checkout follows this package on sys.path.  A failing sample
-    is logged and skipped, as in the reference; samples are written by a small thread pool."""
+    is logged and skipped, as in the reference; samples are written by a small thread pool.
+
+    With hp.vocoder == "hip" the wavs come from the batched GPU Griffin-Lim (b2s_hip.vocoder): every sample with at least 2 frames
+    is vocoded in one call before the pool starts and written with the package's save_wav; `_trim.wav` needs the reference's
+    trim_silence_intervals (librosa).  If the vocoder fails as a whole, that is logged and the .npy files are still written."""
     import threading
     import traceback
     from concurrent.futures import ThreadPoolExecutor
@@ -250,13 +254,29 @@ def save_eval_results(names, mel_pre, mel_aft, alignments, input_lengths, genera
     except Exception:                       # matplotlib / fastdtw are optional
         plot_attn = plot_mel = None
     os.makedirs(output_dir, exist_ok=True)
+    gpu_wavs = None
+    if hp.vocoder == "hip":
+        mel2wav = None                      # the reference's CPU vocoder is not used
+        gpu_wavs, save_wav = _vocode_batch_hip(names, mel_aft, generated_lengths)
+        if save_trimmed_wave and gpu_wavs and trim_silence_intervals is None:
+            logging.warning("vocoder=hip: trimmed waves need the reference's utils.audio.trim_silence_intervals (librosa); "
+                            "writing untrimmed waves only")
+    elif hp.vocoder != "reference":
+        raise ValueError("unknown vocoder %r (expected 'reference' or 'hip')" % hp.vocoder)
 
     def save_one(i):
         try:
             name, n = names[i], int(generated_lengths[i])
             mel = np.asarray(mel_aft[i])[:n]
             np.save(os.path.join(output_dir, '%s.npy' % name), mel)
-            if mel2wav is not None:
+            if gpu_wavs is not None:
+                if i not in gpu_wavs:
+                    raise ValueError("sample %s has %d frames; the vocoder needs at least 2" % (name, n))
+                wav = gpu_wavs[i]
+                save_wav(wav, os.path.join(output_dir, '%s.wav' % name))
+                if save_trimmed_wave and trim_silence_intervals is not None:
+                    save_wav(trim_silence_intervals(wav), os.path.join(output_dir, '%s_trim.wav' % name))
+            elif mel2wav is not None:
                 wav = mel2wav(mel)
                 save_wav(wav, os.path.join(output_dir, '%s.wav' % name))
                 if save_trimmed_wave:
@@ -274,3 +294,34 @@ def save_eval_results(names, mel_pre, mel_aft, alignments, input_lengths, genera
     with ThreadPoolExecutor(max_workers=4) as pool:
         list(pool.map(save_one, range(len(names))))
     logging.info('[%s] Finished saving evals in %.2f secs: ' % (threading.current_thread().name, time.time() - tic) + str(names))
+
+
+def _vocode_batch_hip(names, mel_aft, generated_lengths):
+    """vocoder=hip: one mel2wav_batch call for every sample with a valid length (>= 2 frames).  Returns ({sample index: wav},
+    the package's save_wav), or (None, None) after a failure of the whole call, which is logged."""
+    import traceback
+
+    import numpy as np
+    try:
+        from b2s_hip import vocoder
+        ok = []
+        for i in range(len(names)):
+            try:
+                n = int(generated_lengths[i])
+            except Exception:
+                continue
+            if 2 <= n <= np.asarray(mel_aft[i]).shape[0]:
+                ok.append((i, n))
+        if not ok:
+            return {}, vocoder.save_wav
+        tmax = max(n for _, n in ok)
+        mels = np.zeros([len(ok), tmax, hp.num_mels], dtype=np.float32)
+        for j, (i, n) in enumerate(ok):
+            mels[j, :n] = np.asarray(mel_aft[i])[:n]
+        wav, lens = vocoder.mel2wav_batch(mels, [n for _, n in ok])
+        wav = wav.cpu().numpy()
+        return {i: wav[j, :lens[j]] for j, (i, _) in enumerate(ok)}, vocoder.save_wav
+    except Exception:
+        logging.error('GPU vocoder failed for ' + str(list(names)) + '; writing mel .npy files only')
+        logging.error(traceback.format_exc())
+        return None, None
