@@ -1,5 +1,5 @@
 #!/bin/bash
-# Build libb2s_hip.so and libb2s_vocoder.so for gfx950 (MI355X).  hipcc cross-compiles without a GPU.
+# Build libb2s_hip.so, libb2s_vocoder.so and libb2s_metrics.so for gfx950 (MI355X).  hipcc cross-compiles without a GPU.
 #   build.sh            only what changed
 #   build.sh --clean    recompile every source (what __graft_entry__.build() runs)
 #   build.sh --lab      measurement build with -DB2S_LAB (B2S_LAB_* environment switches that change results: skip the encoder, drop the
@@ -31,4 +31,10 @@ if [ "$1" != "--lab" ]; then
     hipcc $FLAGS -shared vocoder/vocoder.hip -o $VOUT
   fi
   echo "built $VOUT"
+  # batched FastDTW / MSE-after-DTW eval metric: a library of its own too (include/b2s_metrics.h)
+  MOUT=../libb2s_metrics.so
+  if [ "$1" = "--clean" ] || [ ! -f $MOUT ] || [ metrics/dtw.hip -nt $MOUT ] || [ ../../include/b2s_metrics.h -nt $MOUT ]; then
+    hipcc $FLAGS -shared metrics/dtw.hip -o $MOUT
+  fi
+  echo "built $MOUT"
 fi

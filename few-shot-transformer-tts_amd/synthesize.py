@@ -60,7 +60,11 @@ def eval_batch(model_eval, data, use_bar=True, bar_interval=10, use_graph=True, 
     stop.  Measured on MI355X (64 x 1000 frames): 1 / 2 / 4 lanes = 1.03 / 1.01 / 1.06 ms per frame step -- the frame loop
     is bound by the ~5 us the command processor needs per kernel dispatch, which concurrent streams share, so the default
     stays one lane (B2S_DECODE_LANES overrides); the option is for batches too large for one KV-cache allocation.
-    device_results=True returns torch tensors on the device instead of NumPy arrays (no host copy)."""
+    device_results=True returns torch tensors on the device instead of NumPy arrays (no host copy).
+    hp.mse_dtw == "hip" rebinds the reference's utils.infolog.calculate_mse_dtw to the GPU metric first (b2s_hip.metrics.install:
+    eval.py reaches this function after hp.parse and before every MSE-after-DTW call); the default "reference" leaves it alone."""
+    from b2s_hip import metrics
+    metrics.install(hp)
     with torch.no_grad():
         tic = time.time()
         batch = copy.copy(data)

@@ -1,0 +1,48 @@
+/* C ABI of libb2s_metrics.so: batched FastDTW (fastdtw 0.3.4 semantics, euclidean distance) and the MSE-after-DTW eval metric
+ * for gfx950.
+ *
+ * Utterances are packed ragged: frame f of pair b is row x_offsets[b] + f of x (x_offsets = exclusive prefix sum of the lengths,
+ * B + 1 int32 entries on the device), fp32 rows of `dim` features, 1 <= dim <= 256; the same for y.  Distances, the pyramid and the
+ * cumulative costs are fp64.  radius >= 1 is fastdtw(x, y, radius); radius == -1 is the exact dtw(x, y) (full matrix); radius 0 is
+ * refused (fastdtw 0.3.4 cannot backtrack through its window for odd lengths).  Every call launches on the caller's stream, creates
+ * no stream or graph and does not synchronise.  Return codes: 0 = ok, otherwise b2s_met_last_error() holds the message (argument
+ * checks need no GPU; nothing aborts).
+ */
+#ifndef B2S_METRICS_H
+#define B2S_METRICS_H
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* keep only the voiced frames (rows whose maximum over the features is > 0) of each side before the DTW, as the reference's
+ * calculate_mse_dtw does; path indices then refer to the voiced frames */
+#define B2S_MET_VOICED_ONLY 1
+
+/* status_out values */
+#define B2S_MET_OK 0
+#define B2S_MET_EMPTY 1       /* one side has no (voiced) frame: cost, mse = NaN, path_len = 0 (the reference's None) */
+#define B2S_MET_FAILED 2      /* offsets inconsistent with total / max arguments, or a path longer than its path_offsets slot */
+
+int b2s_met_version(void);
+const char *b2s_met_last_error(void);
+
+/* Workspace bytes for one b2s_met_dtw call with these sizes; 0 on an argument error (message set).  max_x / max_y bound every
+ * pair's length (the on-chip plan is sized by them). */
+size_t b2s_met_dtw_ws_bytes(int B, int total_x, int total_y, int max_x, int max_y, int dim, int radius, int flags);
+
+/* cost_out[B] f64 = D[len_x, len_y]; mse_out[B] f64 = mean((x[path_x] - y[path_y])^2) over path length x dim (fp64 over the fp32
+ * inputs); path_len_out[B] int32; status_out[B] int32 (B2S_MET_*).  path_out (nullable): int32 (i, j) pairs, pair b's path written
+ * in order from pair index path_offsets[b]; path_offsets (B + 1 int32 on the device, required with path_out) gives each pair a slot
+ * of path_offsets[b + 1] - path_offsets[b] >= len_x + len_y - 1 pairs. */
+int b2s_met_dtw(const float *x, const int32_t *x_offsets, int total_x, int max_x, const float *y, const int32_t *y_offsets,
+                int total_y, int max_y, int B, int dim, int radius, int flags, double *cost_out, double *mse_out,
+                int32_t *path_len_out, int32_t *status_out, int32_t *path_out, const int32_t *path_offsets, void *ws,
+                size_t ws_bytes, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
