@@ -199,12 +199,6 @@ class GradBucketer(object):
                 raise RuntimeError("gradient exchange covered [0, %d) of %d elements (ranges %s): a backward stage did not report"
                                    % (pos, self.flat.numel(), self.launched[:4]))
 
-    def unpack_all(self):
-        """consume_wire: write the reduced gradients of the last step back into the fp32 buffer (tests / diagnostics)."""
-        if self.wire is not None:
-            for lo, hi in self.launched:
-                self.unpack(self.wire[lo:hi], self.flat[lo:hi])
-
     def abort(self):
         """Wait for what was launched and drop the rest (a stage hook failed; the step is being abandoned)."""
         for w, _lo, _hi in self._works:

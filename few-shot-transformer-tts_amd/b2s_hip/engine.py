@@ -397,10 +397,6 @@ class HipEngine(object):
 
 
 # ====================================================================================== autograd plumbing
-def _param_list(module):
-    return [(n, p) for n, p in module.named_parameters()]
-
-
 class EncoderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, eng, prefix, names, inputs, lens32, spk, lang, train, *params):

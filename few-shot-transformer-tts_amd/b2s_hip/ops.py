@@ -15,10 +15,6 @@ def _rup8(x):
     return (x + 7) // 8 * 8
 
 
-def _esz(dtype):
-    return 2 if dtype else 4
-
-
 def to_compute(x, dtype):
     """fp32 tensor -> compute-dtype device buffer (bf16 raw bits as int16 tensor, or the tensor itself)."""
     x = x.contiguous()

@@ -91,8 +91,6 @@ __device__ inline bf16x8_t pack8(const f32x4_t& a, const f32x4_t& b) {
 
 // acc[dt] (+)= sum over the tile's 64 rows of  tile[row][dt*16 + i] * w[row][j]     (w in the MFMA C layout of a
 // [64 rows x 16] block: w[t][r] belongs to row t*16 + lg*4 + r, column li)          -> result col = li, row = dt*16+lg*4+r
-template <typename T, int DH, int LD>
-__device__ inline void second_product(f32x4_t (&acc)[DH / 16], const T* tile, const f32x4_t (&w)[4], int li, int lg);
 template <int DH, int LD>
 __device__ inline void second_product_f32(f32x4_t (&acc)[DH / 16], const float* tile, const f32x4_t (&w)[4], int li, int lg) {
 #pragma unroll
@@ -314,21 +312,6 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 3 : 1) void attn_fwd_kernel(A
 }
 
 // ================================================================================================ backward
-// D[z, q] = sum_d dO[q][d] * O[q][d]
-template <typename T>
-__global__ void attn_bwd_prep_kernel(const T* dO, const T* O, int ldo, float* D, int H, int Lq, int dh, long rows) {
-    const int lane = threadIdx.x & 63;
-    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);           // r = (b*Lq + q)*H + h
-    if (r >= rows) return;
-    const int h = (int)(r % H);
-    const long bq = r / H;
-    const int q = (int)(bq % Lq), b = (int)(bq / Lq);
-    float acc = 0.f;
-    for (int d = lane; d < dh; d += 64) acc += TT<T>::ld(dO + bq * ldo + h * dh + d) * TT<T>::ld(O + bq * ldo + h * dh + d);
-    acc = wave_sum(acc);
-    if (lane == 0) D[((long)b * H + h) * Lq + q] = acc;
-}
-
 // workgroups per CU the backward kernels are compiled for (2: up to 256 registers per lane; 3: 168).  dQ fits 166 registers without spilling and is
 // latency-bound like the forward kernel: 48.0 -> 43.1 us per launch at 3 (same box, rocprofv3), step 7.11 -> 7.08 ms; dK / dV spills 145 registers
 // at 168 (45 -> 118 us) and stays at 2

@@ -282,14 +282,13 @@ void plan_decode(const b2s_model* m, b2s_decode_state& s, Arena& a) {
     s.a3 = a.f32((long)B * D); s.x = a.f32((long)B * D); s.mean = a.f32(B); s.rstd = a.f32(B);
     s.h = a.T((long)B * D, esz); s.qkv = a.T((long)B * 3 * D, esz); s.ctx = a.T((long)B * D, esz); s.f = a.T((long)B * 4 * D, esz);
     s.outT = a.T((long)B * D, esz); s.mel_step = a.f32((long)B * cf.num_mels); s.stop_step = a.f32(B);
-    constexpr bool no_fused = false;          // A/B switch: one kernel per op (round-1 path)
     s.ns_ffn = b2s_df_ffn_slices(m->dtype, D, H, 4 * D);
-    s.fused = !no_fused && b2s_df_supported(m->dtype, D, H, 4 * D, cf.num_mels, cf.prenet_hidden, std::max(T, S));
+    s.fused = b2s_df_supported(m->dtype, D, H, 4 * D, cf.num_mels, cf.prenet_hidden, std::max(T, S));
     if (s.fused) {
         const int ns = std::max(H, s.ns_ffn);
         for (int i = 0; i < 2; ++i) { s.Xpp[i] = a.f32((long)B * D); s.Ppp[i] = a.f32((long)ns * B * D); }
         s.done_cnt = (int*)a.take(256);
-        const int dh = D / H, F = 4 * D, HP = cf.prenet_hidden, NM = cf.num_mels;
+        const int F = 4 * D, HP = cf.prenet_hidden, NM = cf.num_mels;
         const std::string p = "decoder.decoder.";
         s.packs.clear();
         auto add = [&](const std::string& n, int N, int K) { s.packs.push_back({n, N, K, a.T((long)N * K, 2)}); };

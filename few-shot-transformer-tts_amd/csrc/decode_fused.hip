@@ -604,7 +604,7 @@ __device__ __forceinline__ void l2_warm(const void* base, long bytes, int my, in
 template <typename T, bool SELF, bool FAST>
 __global__ __launch_bounds__(NT) void k_df_attn(DfAttn a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    constexpr int VE = DV<T>::VE, UB = UBA;
+    constexpr int UB = UBA;
     const DfCommon& c = a.c;
     const int tid = threadIdx.x, D = c.D, dh = a.dh, H = a.H;
     const int h = blockIdx.x % H, b0 = (blockIdx.x / H) * UB, t = *c.t;

@@ -442,11 +442,6 @@ int end_stage(const b2s_model* m, hipStream_t st, int stage, bool drain, bool fo
 
 struct AttnScratch { float* S; float* dP; void* dS; };
 struct GuidedArgs { float* rows = nullptr; const int* qlen = nullptr; const float* scale = nullptr; float inv2s2 = 0.f; };
-// fused attention (attention.hip) unless B2S_ATTN_V1 is set (A/B switch: materialised logits through the GEMM)
-bool use_flash(int dh) {
-    constexpr bool v1 = false;
-    return !v1 && b2s_flash_supported(dh);
-}
 AttnArgs flash_args(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int B, int H, int Lq, int Lk, int dh,
                     int mask_mode, const int* klen, DropCfg drop, float* lse) {
     AttnArgs a;
@@ -460,7 +455,7 @@ int attn_core_fwd(int dtype, hipStream_t st, const void* q, int ldq, const void*
                   void* ctx, int ldc, int B, int H, int Lq, int Lk, int dh, int mask_mode, const int* klen,
                   const float* bias, long bias_sb, long bias_sq, DropCfg drop, float* S, void* P, void* Pd, float* lse = nullptr,
                   const GuidedArgs* ga = nullptr, const int* qskip = nullptr, const int* qoff = nullptr, const int* koff = nullptr) {
-    if (lse && !bias && use_flash(dh)) {
+    if (lse && !bias && b2s_flash_supported(dh)) {
         AttnArgs a = flash_args(q, ldq, k, ldk, v, ldv, B, H, Lq, Lk, dh, mask_mode, klen, drop, lse);
         a.out = ctx; a.ldo = ldc; a.qskip = qskip; a.qoff = qoff; a.koff = koff;
         if (ga) { a.ga_rows = ga->rows; a.qlen = ga->qlen; a.ga_inv2s2 = ga->inv2s2; }
@@ -491,7 +486,7 @@ int attn_core_bwd(int dtype, hipStream_t st, const void* dctx, int ldc, const vo
                   float* lse = nullptr, const void* O = nullptr, int mask_mode = 0, const int* klen = nullptr,
                   const GuidedArgs* ga = nullptr, const int* qskip = nullptr, const int* qoff = nullptr, const int* koff = nullptr,
                   hipStream_t st_dkv = nullptr, hipEvent_t ev_dq = nullptr) {
-    if (lse && use_flash(dh)) {
+    if (lse && b2s_flash_supported(dh)) {
         AttnArgs a = flash_args(q, ldq, k, ldk, v, ldv, B, H, Lq, Lk, dh, mask_mode, klen, drop, lse);
         a.qskip = qskip; a.qoff = qoff; a.koff = koff;
         a.dout = dctx; a.ldo = ldc; a.dsum = dP; a.dq = dq; a.dk = dk; a.dv = dv; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
@@ -586,7 +581,7 @@ void plan_attn(Arena& a, AttnSave& s, int esz, long M, int D, int B, int H, int 
     s.qkv = a.T(M * (cross ? D : 3 * D), esz);
     if (cross) { s.kv = a.T(Mk * 2 * D, esz); s.ldkv = 2 * D; }        // (re-pointed into the ctx-wide K/V buffer by plan_decoder when there is one)
     const long pn = (long)B * H * Lq * s.ldp;
-    if (use_flash(D / H)) {
+    if (b2s_flash_supported(D / H)) {
         s.lse = a.f32((long)B * H * Lq);
         s.P = s.Pd = nullptr;
     } else {
@@ -755,16 +750,15 @@ extern "C" int b2s_model_create(const b2s_config* cfg, b2s_model** out) {
     m->cfg = c; m->dtype = c.compute_dtype; m->esz = c.compute_dtype ? 2 : 4; m->Dm = Dm;
     {
         static const bool no_fused = getenv("B2S_ENC_FUSED") && atoi(getenv("B2S_ENC_FUSED")) == 0;            // A/B switch: the unfused encoder
-        // partial sublayer outputs in bf16 (default): the 8 slabs of a sublayer are written and re-read once each -- 26 MB instead of 52 MB per
-        // sublayer and direction; the sum and the residual stream stay fp32 (same rounding point as every other bf16 operand of the step).
-        // B2S_ENC_SLAB_BF16=0: fp32 slabs.  Measured (profiles/NOTES_r04.md): 7.76 -> 7.70 ms per step
-        constexpr int slab_bf16 = 1;
         m->enc_fused = m->dtype == 1 && !no_fused && c.n_encoder_layer > 0 && c.n_encoder_layer * 4 <= 24 &&
                        b2s_encf_supported(c.encoder_hidden, c.n_attention_head, 4 * c.encoder_hidden, 1);
-        m->enc_slab_bf16 = slab_bf16;
+        // partial sublayer outputs in bf16: the 8 slabs of a sublayer are written and re-read once each -- 26 MB instead of 52 MB per
+        // sublayer and direction; the sum and the residual stream stay fp32 (same rounding point as every other bf16 operand of the step).
+        // Measured against fp32 slabs (profiles/NOTES_r04.md): 7.76 -> 7.70 ms per step
+        m->enc_slab_bf16 = 1;
         static const bool no_dx16 = getenv("B2S_DX_BF16") && atoi(getenv("B2S_DX_BF16")) == 0;
         auto fast_ln = [](int d) { return d == 512 || d == 768; };
-        m->dx_bf16 = m->dtype == 1 && !no_dx16 && true && fast_ln(c.encoder_hidden) && fast_ln(c.decoder_hidden);
+        m->dx_bf16 = m->dtype == 1 && !no_dx16 && fast_ln(c.encoder_hidden) && fast_ln(c.decoder_hidden);
     }
     build_layout(m);
     const size_t n = m->tinfo.size();
@@ -1003,7 +997,7 @@ extern "C" int b2s_model_bind(b2s_model* m, void* const* data_host, void* const*
         m->grad[i] = grad_host ? grad_host[i] : nullptr;
     }
     // compute-dtype shadows
-    if (m->dtype == 1 && !m->kv_cat && m->cfg.n_decoder_layer > 0 && true) {
+    if (m->dtype == 1 && !m->kv_cat && m->cfg.n_decoder_layer > 0) {
         const int L = m->cfg.n_decoder_layer, D = m->cfg.decoder_hidden;
         B2S_HIP(hipMalloc(&m->kv_cat, (size_t)L * 2 * D * D * 2));
         m->owned.push_back(m->kv_cat);
@@ -1051,7 +1045,7 @@ extern "C" int b2s_model_bind(b2s_model* m, void* const* data_host, void* const*
             if (hipMalloc(&m->sk_ws[i], m->sk_ws_floats * sizeof(float)) == hipSuccess) m->owned.push_back(m->sk_ws[i]);
             else { m->sk_ws[i] = nullptr; (void)hipGetLastError(); }      // (no slab: that stream's split-K launches use atomics)
     }
-    if (!m->aux && true) {
+    if (!m->aux) {
         // (a lowest-priority second stream was measured: no change -- a weight-gradient workgroup holds its CU for ~110 us once it
         // has started, whatever the queue priorities say)
         B2S_TRY(aux_stream_of(&m->aux));
@@ -1422,7 +1416,7 @@ extern "C" int b2s_encoder_backward(b2s_model* m, b2s_ctx* c, const float* d_mem
     B2S_CHECK(c && c->kind == 1 && d_memory, "bad encoder context");
     const b2s_config& cf = m->cfg;
     hipStream_t st = S_(stream);
-    const int B = c->B, S = c->S, D = cf.encoder_hidden, H = cf.n_attention_head, Dm = m->Dm, dt = m->dtype;
+    const int B = c->B, S = c->S, D = cf.encoder_hidden, H = cf.n_attention_head, Dm = m->Dm;
     const long M = (long)B * S;
     const float pt = c->train ? cf.transformer_dropout_rate : 0.f;
     Arena a; a.base = c->ws; a.cap = c->ws_bytes;
@@ -1606,7 +1600,7 @@ extern "C" int b2s_decoder_forward(b2s_model* m, const float* memory, const int3
     {
         std::vector<int> lens;
         lens.swap(m->ragged_lens);                        // consumed by this call, whatever happens below
-        if (padded_unobserved && (int)lens.size() == B && B <= 64 && use_flash(dh)) {
+        if (padded_unobserved && (int)lens.size() == B && B <= 64 && b2s_flash_supported(dh)) {
             hoff.assign(1, 0);
             for (int b = 0; b < B; ++b) {
                 if (lens[b] < 1 || lens[b] > T) { delete c; return b2s_fail(__FILE__, __LINE__, "b2s_decoder_compact_rows: target length %d of utterance %d outside [1, %d]", lens[b], b, T); }
@@ -1800,7 +1794,7 @@ extern "C" int b2s_decoder_backward(b2s_model* m, b2s_ctx* c, const float* d_mel
     // side stream (engine.h): the dK / dV kernels of the encoder-decoder attentions leave this stream
     m->side_ev = nullptr;
     struct SideReset { b2s_model* m; ~SideReset() { m->side_ev = nullptr; } } side_reset{m};
-    const bool side = m->side && m->side != st && sc.dkvcat && sc.dctx_x && dt == 1 && use_flash(dh);
+    const bool side = m->side && m->side != st && sc.dkvcat && sc.dctx_x && dt == 1 && b2s_flash_supported(dh);
     if (side && m->side_evs.empty()) {
         m->side_evs.resize(16);
         for (auto& e : m->side_evs) B2S_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1966,9 +1960,8 @@ extern "C" int b2s_postnet_forward(b2s_model* m, const float* inputs, const int3
     const float pd = train ? cf.decoder_dropout_rate : 0.f;
     // Training: the batch statistics are column sums taken by the conv GEMM's epilogue (GemmEpilogue::colstat) and turned into mean /
     // rstd / running statistics by the normalisation kernel itself: conv + one row kernel per layer (was conv + memset + two reduction
-    // passes + finalize + apply).  B2S_BN_SEPARATE=1 keeps the separate two-pass statistics (A/B switch).
-    constexpr bool bn_separate = false;
-    const bool fused_stats = train && !bn_separate && M > 1;
+    // passes + finalize + apply).  Evaluation (running statistics) and a one-row batch (a statistics pass of its own) take the statistics first.
+    const bool fused_stats = train && M > 1;
     auto run = [&]() -> int {
         B2S_TRY(ro_cast(dt, inputs, c->u[0], M * cf.num_mels, st));
         if (fused_stats) B2S_HIP(hipMemsetAsync(ps.stat, 0, sizeof(float) * (size_t)n * ps.stat_stride, st));
@@ -2060,9 +2053,8 @@ extern "C" int b2s_postnet_backward(b2s_model* m, b2s_ctx* c, const float* d_out
         hipEvent_t ready = m->next_event();
         B2S_HIP(hipEventRecord(ready, st));
         B2S_HIP(hipStreamWaitEvent(m->aux, ready, 0));
-        constexpr bool in_kernel_gather = false;          // A/B switch: the previous form
         for (GemmArgs& g : dws) {
-            if (ps.col && !in_kernel_gather && g.B.g_cin % 8 == 0) {
+            if (ps.col && g.B.g_cin % 8 == 0) {
                 B2S_TRY(ro_im2col5(dt, g.B.p, g.B.g_len, g.B.g_T, g.B.g_cin, ps.col, (long)g.B.R, m->aux));
                 g.B.p = ps.col; g.B.ld = 5 * g.B.g_cin; g.B.g_cin = 0; g.B.g_T = 0; g.B.g_len = nullptr;
             }

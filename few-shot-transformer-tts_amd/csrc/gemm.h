@@ -56,15 +56,20 @@ struct GemmArgs {
     size_t ws_floats = 0;
 };
 
-// dtype: 0 = fp32 (mfma_f32_16x16x4f32), 1 = bf16 (mfma_f32_16x16x32_bf16, fp32 accumulate)
+// The GEMM entry point (gemm.hip), and the one place that picks the tiled kernel.  dtype: 0 = fp32 (gemm_kernel,
+// mfma_f32_16x16x4f32); 1 = bf16 (mfma_f32_16x16x32_bf16, fp32 accumulate): b2s_gemm_glds256_launch for non-batched problems with
+// M >= 129 (B2S_GEMM256_MIN_M), b2s_gemm_glds_launch otherwise.  (The decode step's weight-streaming kernel and the grouped
+// weight-gradient launch below are called by name.)
 int b2s_gemm_launch(const GemmArgs& g, int dtype, bool ta, bool tb, hipStream_t stream);
-// bf16 LDS-DMA (global_load_lds) + swizzled-LDS main loop (gemm_glds.hip)
+// bf16 128x128-tile LDS-DMA kernel (gemm_glds.hip)
 int b2s_gemm_glds_launch(const GemmArgs& g, bool ta, bool tb, hipStream_t stream);
 // decode-step weight-streaming kernel (gemm_skinny.hip); returns -1 when the problem does not fit it
 int b2s_gemm_skinny_launch(const GemmArgs& g, int dtype, hipStream_t stream);
-// 256x128-tile variant for the large-M forms (gemm_glds256.hip) and the split-K slab reduction shared by both
+// bf16 256-row-tile family (gemm_glds256.hip; tile width, persistent walk and 128-row variant are chosen inside), and the number
+// of 256x128 tiles a problem decomposes into
 long b2s_gemm_glds256_tiles(const GemmArgs& g);
 int b2s_gemm_glds256_launch(const GemmArgs& g, bool ta, bool tb, const bf16_t* zero, hipStream_t stream);
+// split-K slab reduction shared by both bf16 families (gemm_glds.hip)
 int b2s_splitk_reduce_launch(const float* ws, float* dst, int M, int N, int ldc, int splitk, int conv_dw_cin, hipStream_t stream);
 // up to B2S_MAX_GROUP weight-gradient problems (TN form, fp32 accumulate, no split-K) in one launch
 #define B2S_MAX_GROUP 8

@@ -1,18 +1,19 @@
-// MFMA GEMM for gfx950 (MI355X): C = epilogue(op(A) * op(B)), batched, with an optional conv1d
-// (k=5, pad=2) row-gather on either operand.  One kernel template serves every dense contraction
-// of the Transformer-TTS path (reference: every nn.Linear / torch.matmul / nn.Conv1d call in
-// transformer/attention.py:43-47,83,91, transformer/modules.py:11-13, transformer/tacotron.py:50-52,
-// 78,104-105, and their autograd backward forms).
+// GEMM dispatcher (b2s_gemm_launch) and the fp32 MFMA kernel of the parity mode, for gfx950 (MI355X).
+// C = epilogue(op(A) * op(B)), batched, with an optional conv1d (k=5, pad=2) row-gather on either operand: every dense
+// contraction of the Transformer-TTS path has this form (reference: every nn.Linear / torch.matmul / nn.Conv1d call in
+// transformer/attention.py:43-47,83,91, transformer/modules.py:11-13, transformer/tacotron.py:50-52, 78,104-105, and
+// their autograd backward forms).
 //
+// gemm_kernel (fp32, dtype 0):
 //   * 128x128 block tile, 256 threads = 4 waves (2x2), each wave 64x64 = 4x4 MFMA 16x16 tiles.
-//   * bf16: v_mfma_f32_16x16x32_bf16, BK = 64, fp32 accumulate.   fp32: v_mfma_f32_16x16x4_f32
-//     (exact fp32 fma chain, used by the parity mode), BK = 16.
+//   * v_mfma_f32_16x16x4_f32 (exact fp32 fma chain), BK = 16.
 //   * operands are staged HBM -> registers (16-byte loads) -> LDS, double-buffered, one barrier per
 //     K tile; the next tile's global loads are issued before the MFMAs of the current tile.
-//   * a K-contiguous operand is kept [rows][BK+pad] in LDS and read with ds_read_b128 (bf16) /
-//     ds_read_b32 (fp32); an operand whose reduction index is the slow dimension (the "NN"/"TN"
-//     backward forms) is kept [BK][rows+pad] and read with ds_read_b64_tr_b16 (bf16), so no
+//   * a K-contiguous operand is kept [rows][BK+pad] in LDS, an operand whose reduction index is the slow
+//     dimension (the "NN"/"TN" backward forms) [BK][rows+pad]; both are read with ds_read_b32, so no
 //     transposed copy of any activation or weight is ever written to HBM.
+// bf16 (dtype 1) goes to the LDS-DMA kernels: 256-row tiles (gemm_glds256.hip) for non-batched problems taller than
+// one 128-row tile, 128x128 tiles (gemm_glds.hip) for the batched (per-head) and short ones.
 #include <mutex>
 #include "gemm.h"
 #include "gemm_epi.h"
@@ -21,45 +22,19 @@ namespace {
 
 constexpr int BM = 128, BN = 128;
 
-template <typename T> struct Cfg;
-template <> struct Cfg<float>  { static constexpr int BK = 16, KSTEP = 4,  VE = 4; };
-template <> struct Cfg<bf16_t> { static constexpr int BK = 64, KSTEP = 32, VE = 8; };
-
-template <typename T> struct FragT;
-template <> struct FragT<float>  { typedef float type; };
-template <> struct FragT<bf16_t> { typedef bf16x8_t type; };
-
-typedef __attribute__((address_space(3))) bf16x4_t* lds_b64_ptr;
+constexpr int BK = 16, KSTEP = 4, VE = 4;      // K tile, K per MFMA, elements per 16-byte chunk
 
 // ---- fragment loads.  lane: i = lane & 15 (row/col inside the 16-tile), g = lane >> 4 (k group)
-// K-contiguous tile [rows][LD]: element (row0 + i, k0 + g*KPL ..)
+// K-contiguous tile [rows][LD]: element (row0 + i, k0 + g)
 __device__ inline float frag_n(const float* tile, int LD, int row0, int k0, int i, int g) {
     return tile[(row0 + i) * LD + k0 + g];
-}
-__device__ inline bf16x8_t frag_n(const bf16_t* tile, int LD, int row0, int k0, int i, int g) {
-    return *reinterpret_cast<const bf16x8_t*>(tile + (row0 + i) * LD + k0 + g * 8);
 }
 // reduction-major tile [BK][LD] (LD = rows + pad): same logical fragment, gathered by transpose reads
 __device__ inline float frag_t(const float* tile, int LD, int row0, int k0, int i, int g) {
     return tile[(k0 + g) * LD + row0 + i];
 }
-__device__ inline bf16x8_t frag_t(const bf16_t* tile, int LD, int row0, int k0, int i, int g) {
-    // ds_read_b64_tr_b16: within a 16-lane group, lane i receives element (i & 3) of the 8-byte
-    // rows supplied by lanes 4j + (i >> 2), j = 0..3.  Supplying row (k0 + g*8 + (i >> 2)), columns
-    // row0 + (i & 3)*4 .. +3 therefore returns [k0 + g*8 + j][row0 + i], j = 0..3.
-    const bf16_t* p0 = tile + (k0 + g * 8 + (i >> 2)) * LD + row0 + (i & 3) * 4;
-    bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_b64_ptr)(p0));
-    bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_b64_ptr)(p0 + 4 * LD));
-    bf16x8_t r;
-    r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-    r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-    return r;
-}
 __device__ inline f32x4_t mma(float a, float b, f32x4_t c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-__device__ inline f32x4_t mma(bf16x8_t a, bf16x8_t b, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
 // ---- one 16-byte chunk of an operand: stored row r, stored cols c .. c+VE-1 (zero if out of range)
@@ -80,16 +55,15 @@ __device__ inline uint4 load_chunk(const GemmOperand& o, const T* base, int r, i
     return *reinterpret_cast<const uint4*>(base + (long)r * o.ld + c);
 }
 
+// T is always float; the kernel keeps its template form (gemm_kernel<float, TA, TB>) because profiles name it that way
 template <typename T, bool TA, bool TB>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
-    constexpr int BK = Cfg<T>::BK, KSTEP = Cfg<T>::KSTEP, VE = Cfg<T>::VE;
     constexpr int LDN = BK + VE;          // K-contiguous tile row stride (elements)
     constexpr int LDT = 128 + VE;         // reduction-major tile row stride
     constexpr int TILE_A = TA ? BK * LDT : BM * LDN;
     constexpr int TILE_B = TB ? BK * LDT : BN * LDN;
     constexpr int NV = 128 * BK / VE / 256;     // 16-byte vectors per thread per operand tile
     constexpr int VPR_N = BK / VE, VPR_T = 128 / VE;
-    typedef typename FragT<T>::type frag_t_;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     // NOTE: LDS addresses are formed as (shared base + integer offset) everywhere: keeping tile pointers in an
@@ -150,7 +124,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
         const T* tB = smem + 2 * TILE_A + cur * TILE_B;
 #pragma unroll
         for (int ks = 0; ks < BK / KSTEP; ++ks) {
-            frag_t_ fa[4], fb[4];
+            float fa[4], fb[4];
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 fa[t] = TA ? frag_t(tA, LDT, wrow + t * 16, ks * KSTEP, li, lg)
@@ -231,32 +205,30 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
     }
 }
 
-template <typename T, bool TA, bool TB>
+template <bool TA, bool TB>
 int launch_t(const GemmArgs& g, hipStream_t stream) {
-    constexpr int BK = Cfg<T>::BK, VE = Cfg<T>::VE;
     constexpr int LDN = BK + VE, LDT = 128 + VE;
     constexpr int TILE_A = TA ? BK * LDT : BM * LDN;
     constexpr int TILE_B = TB ? BK * LDT : BN * LDN;
-    constexpr size_t smem = 2 * (size_t)(TILE_A + TILE_B) * sizeof(T);
+    constexpr size_t smem = 2 * (size_t)(TILE_A + TILE_B) * sizeof(float);
     static std::once_flag attr_once;
     static hipError_t attr_err = hipSuccess;
     std::call_once(attr_once, [] {
-        attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel<T, TA, TB>),
+        attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel<float, TA, TB>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     });
     B2S_HIP(attr_err);
     dim3 grid(cdiv(g.N, BN), cdiv(g.M, BM), g.batch * g.splitk);
-    hipLaunchKernelGGL((gemm_kernel<T, TA, TB>), grid, dim3(256), smem, stream, g);
+    hipLaunchKernelGGL((gemm_kernel<float, TA, TB>), grid, dim3(256), smem, stream, g);
     B2S_LAUNCH_CHECK();
     return 0;
 }
 
-template <typename T>
-int launch_d(const GemmArgs& g, bool ta, bool tb, hipStream_t s) {
-    if (!ta && !tb) return launch_t<T, false, false>(g, s);
-    if (!ta && tb) return launch_t<T, false, true>(g, s);
-    if (ta && !tb) return launch_t<T, true, false>(g, s);
-    return launch_t<T, true, true>(g, s);
+int launch_fp32(const GemmArgs& g, bool ta, bool tb, hipStream_t s) {
+    if (!ta && !tb) return launch_t<false, false>(g, s);
+    if (!ta && tb) return launch_t<false, true>(g, s);
+    if (ta && !tb) return launch_t<true, false>(g, s);
+    return launch_t<true, true>(g, s);
 }
 
 }  // namespace
@@ -332,7 +304,15 @@ static int gemm_launch_inner(const GemmArgs& g, int dtype, bool ta, bool tb, hip
                                                    !g.epi.relu_aux && !g.epi.drop.thresh)),
               "gemm: split-K needs a linear fp32 accumulate epilogue");
     B2S_CHECK(!g.epi.kv_k, "gemm: the cache-append fusion exists in the decode-step kernel only (M <= 64, K %% 32 == 0)");
-    constexpr bool use_v1 = false;         // A/B switch: register-staged bf16 main loop
-    if (dtype && !use_v1) return b2s_gemm_glds_launch(g, ta, tb, stream);
-    return dtype ? launch_d<bf16_t>(g, ta, tb, stream) : launch_d<float>(g, ta, tb, stream);
+    if (!dtype) return launch_fp32(g, ta, tb, stream);
+    // bf16 tile shape: 256-row tiles with 64-deep K steps for every non-batched problem taller than one 128-row tile -- measured
+    // faster in the training step down to the M = 1596 encoder shapes (half the barriers per FLOP); the 128x128 kernel keeps the
+    // batched (per-head) and short problems.  B2S_GEMM256_MIN_M overrides.
+    static const long min_m = getenv("B2S_GEMM256_MIN_M") ? atol(getenv("B2S_GEMM256_MIN_M")) : 129;
+    if (g.batch == 1 && g.M >= min_m) {
+        const bf16_t* zero = b2s_gemm_zero_page();
+        if (!zero) return 1;               // (b2s_fail has recorded the HIP error)
+        return b2s_gemm_glds256_launch(g, ta, tb, zero, stream);
+    }
+    return b2s_gemm_glds_launch(g, ta, tb, stream);
 }

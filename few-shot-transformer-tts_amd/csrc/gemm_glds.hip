@@ -1,8 +1,9 @@
-// bf16 MFMA GEMM, second-generation main loop for gfx950: operands go HBM -> LDS directly with
-// global_load_lds_dwordx4 (LDS-DMA, no staging VGPRs, no ds_write pass), LDS tiles are dense and XOR-swizzled so
-// that both the K-contiguous fragment reads (ds_read_b128) and the reduction-major fragment reads
-// (ds_read_b64_tr_b16) are bank-conflict free, and the next K tile's DMA is in flight while the current tile's
-// MFMAs run (one s_barrier per K tile).  Same contract / epilogues as gemm_kernel in gemm.hip.
+// bf16 MFMA GEMM with 128x128 tiles for gfx950, for the batched and short problems (gemm.hip's dispatcher sends the
+// others to gemm_glds256.hip).  Operands go HBM -> LDS directly with global_load_lds_dwordx4 (LDS-DMA, no staging
+// VGPRs, no ds_write pass), LDS tiles are dense and XOR-swizzled so that both the K-contiguous fragment reads
+// (ds_read_b128) and the reduction-major fragment reads (ds_read_b64_tr_b16) are bank-conflict free, and the next
+// K tile's DMA is in flight while the current tile's MFMAs run (one s_barrier per K tile).  Same contract /
+// epilogues as gemm_kernel in gemm.hip.
 //
 // The LDS-DMA writes lane-linearly (wave base + lane*16 B), so the swizzle is applied on the SOURCE side: lane L
 // of a DMA instruction owns LDS slot L and fetches the global chunk whose swizzled position is L.
@@ -15,7 +16,6 @@
 // DMA / whole-line fetch / register loads, results in profiles/README.md -- lived here as #ifdefs; they were removed from the
 // production kernel and can be re-created from commit a6102c4 with tools/gemm_lab.hip.)
 #include <algorithm>
-#include <cstdlib>
 #include <mutex>
 #include "gemm.h"
 #include "gemm_epi.h"
@@ -263,8 +263,7 @@ int launch_t(const GemmArgs& g_in, hipStream_t stream) {
 }  // namespace
 
 int b2s_splitk_reduce_launch(const float* ws, float* dst, int M, int N, int ldc, int splitk, int conv_dw_cin, hipStream_t stream) {
-    constexpr bool conv_v1 = false;        // A/B switch
-    if (conv_dw_cin > 0 && N == 5 * conv_dw_cin && !conv_v1) {
+    if (conv_dw_cin > 0 && N == 5 * conv_dw_cin) {
         const long pairs = (long)M * conv_dw_cin;
         hipLaunchKernelGGL(splitk_reduce_conv_kernel, dim3((int)std::min<long>((pairs + 255) / 256, 2048)), dim3(256), 0, stream, ws, dst, M, N, ldc, splitk,
                            conv_dw_cin);
@@ -292,12 +291,6 @@ const bf16_t* b2s_gemm_zero_page() { return ensure_globals() ? nullptr : g_zero_
 
 int b2s_gemm_glds_launch(const GemmArgs& g, bool ta, bool tb, hipStream_t stream) {
     B2S_TRY(ensure_globals());
-    // tile shape: 256-row tiles with 64-deep K steps (gemm_glds256.hip) for every non-batched problem taller than one
-    // 128-row tile -- measured faster in the training step down to the M = 1596 encoder shapes (half the barriers per
-    // FLOP); the 128x128 kernel keeps the batched (per-head) and short problems.  B2S_GEMM256_MIN_M overrides.
-    static const long min_m = getenv("B2S_GEMM256_MIN_M") ? atol(getenv("B2S_GEMM256_MIN_M")) : 129;
-    if (g.batch == 1 && g.M >= min_m)
-        return b2s_gemm_glds256_launch(g, ta, tb, g_zero_page, stream);
     const bool gather = g.A.g_cin > 0 || g.B.g_cin > 0;
     if (gather) {       // conv1d forms: forward / backward-data (NT, gather on A) and weight gradient (TN, gather on B)
         if (!ta && !tb) return launch_t<false, false, true>(g, stream);

@@ -898,8 +898,7 @@ int b2s_gemm_glds256_grouped_launch(const GemmArgs* probs, int n, const bf16_t* 
     B2S_CHECK(n >= 1 && n <= B2S_MAX_GROUP, "grouped GEMM: %d problems (max %d)", n, B2S_MAX_GROUP);
     b2s_gemm_group grp;
     grp.n = n;
-    constexpr int xcd_order = 1;
-    grp.order = xcd_order;
+    grp.order = 1;                                     // XCD-contiguous tile order over the whole list
     // Launch order = dispatch order.  Tiles cost ~K; with one workgroup per CU the makespan of "deepest first" against
     // "shallowest first" is decided by list scheduling on the CU count (288 tiles of a decoder layer: 252 deep + 36 shallow --
     // shallow first lets the 36 early finishers take the last 32 deep tiles, deep first leaves 32 shallow tiles to 4 CUs)
@@ -925,16 +924,13 @@ int b2s_gemm_glds256_grouped_launch(const GemmArgs* probs, int n, const bf16_t* 
     const long deep = makespan(true), shallow = makespan(false);
     if (deep <= shallow) makespan(true);               // (leaves `order` as chosen)
     int tiles = 0;
-    constexpr int split = 1;
     for (int k = 0; k < n; ++k) {
         const GemmArgs& g = probs[order[k]];
         B2S_CHECK(g.batch == 1 && g.c_fp32 && g.A.g_cin == 0 && g.B.g_cin == 0, "grouped GEMM: problem %d is not a plain fp32 dW", order[k]);
-        B2S_CHECK(g.epi.accumulate || split == 1, "grouped GEMM: split K needs an accumulating output (problem %d overwrites)", order[k]);
-        // B2S_DW_SPLIT = 2: every tile's K walk in two halves.  The weight-gradient groups share the chip with the backward's main-stream
-        // kernels; ~290 tiles of 127 K steps each on fewer than 256 free CUs need a second full-length round, half-length units pack better.
-        grp.p[k] = g; grp.p[k].splitk = (split > 1 && g.K >= 4 * split * t256::BK) ? split : 1;
+        // every tile walks its whole K (the kernel can also split a problem's K walk over several tiles: p[k].splitk > 1)
+        grp.p[k] = g; grp.p[k].splitk = 1;
         grp.tile0[k] = tiles;
-        tiles += cdiv(g.M, t256::BM) * cdiv(g.N, 128) * grp.p[k].splitk;
+        tiles += cdiv(g.M, t256::BM) * cdiv(g.N, 128);
     }
     grp.tile0[n] = tiles;
     constexpr size_t smem = (size_t)t256::NSTAGE * t256::STAGE_BYTES;
@@ -960,7 +956,7 @@ extern "C" int b2s_gemm_set_tile_policy(int policy) {
     return 0;
 }
 
-// number of 256x128 tiles a problem decomposes into (the dispatcher in gemm_glds.hip uses it to pick the tile shape)
+// number of 256x128 tiles a problem decomposes into (the engine balances its weight-gradient groups by it)
 long b2s_gemm_glds256_tiles(const GemmArgs& g) { return (long)cdiv(g.M, t256::BM) * cdiv(g.N, 128) * g.batch * std::max(1, g.splitk); }
 
 int b2s_gemm_glds256_launch(const GemmArgs& g, bool ta, bool tb, const bf16_t* zero, hipStream_t stream) {
@@ -970,8 +966,7 @@ int b2s_gemm_glds256_launch(const GemmArgs& g, bool ta, bool tb, const bf16_t* z
             // forward / backward-data convolution over >= 64-aligned channel counts: aligned gather on the producer waves
             const bool aligned = g.A.g_cin > 0 && g.B.g_cin == 0 && g.A.g_cin % t256::BK == 0 && g.K % t256::BK == 0 && g.splitk == 1 &&
                                  (long)g.A.R * g.A.ld < (1L << 29) && (long)g.B.R * g.B.ld < (1L << 30) && g.A.g_T > 0;
-            constexpr bool no_fast = false;      // A/B switch
-            if (aligned && !no_fast) return t256::launch256_t<false, false, 2>(g, zero, stream);
+            if (aligned) return t256::launch256_t<false, false, 2>(g, zero, stream);
             return t256::launch256_t<false, false, 1>(g, zero, stream);
         }
         if (ta && tb) return t256::launch256_t<true, true, 1>(g, zero, stream);

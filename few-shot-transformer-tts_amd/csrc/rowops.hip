@@ -704,26 +704,6 @@ __global__ void k_bn_eval_stats(const float* rm, const float* rv, float* mean, f
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c < C) { mean[c] = rm[c]; rstd[c] = 1.f / sqrtf(rv[c] + eps); }
 }
-template <typename T>
-__global__ void k_bn_apply(const float* y, const float* mean, const float* rstd, const float* gamma, const float* beta,
-                           int use_tanh, T* outT, float* out32, const float* add32, int M, int C, DropCfg drop) {
-    const int nq = C >> 2;
-    const long total = (long)M * nq;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        int m = (int)(i / nq), c = (int)(i - (long)m * nq) * 4;
-        float4 v = ld4(y + (long)m * C + c), mu = ld4(mean + c), rs = ld4(rstd + c), g = ld4(gamma + c), be = ld4(beta + c);
-        float4 o;
-        o.x = (v.x - mu.x) * rs.x * g.x + be.x; o.y = (v.y - mu.y) * rs.y * g.y + be.y;
-        o.z = (v.z - mu.z) * rs.z * g.z + be.z; o.w = (v.w - mu.w) * rs.w * g.w + be.w;
-        if (use_tanh) { o.x = tanhf(o.x); o.y = tanhf(o.y); o.z = tanhf(o.z); o.w = tanhf(o.w); }
-        o = drop4(o, drop, (uint32_t)((long)m * C + c));
-        if (outT) st4(outT + (long)m * C + c, o);
-        if (out32) {
-            if (add32) { float4 a = ld4(add32 + (long)m * C + c); o.x += a.x; o.y += a.y; o.z += a.z; o.w += a.w; }
-            st4(out32 + (long)m * C + c, o);
-        }
-    }
-}
 template <typename TD>
 __device__ inline float bn_dz(const TD* dout, const float* y, long off, int c, const float* mean, const float* rstd,
                               const float* gamma, const float* beta, int use_tanh, const DropCfg& drop, float* xhat) {
@@ -1221,9 +1201,6 @@ __global__ void k_add(const float* a, const float* b, float* o, long n) {
 __global__ void k_add3(const float* a, const float* b, const float* c, float* o, long n) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) o[i] = (a[i] + b[i]) + c[i];
 }
-__global__ void k_fill(float* p, float v, long n) {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) p[i] = v;
-}
 
 inline int ew_grid(long n, int per = 256) { long g = (n + per - 1) / per; return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g)); }
 
@@ -1246,8 +1223,7 @@ int ro_layernorm_fwd(int dtype, const float* x, const float* gamma, const float*
                      int ldy32, float* mean, float* rstd, int M, int D, float eps, const int* row_len,
                      int rows_per_batch, hipStream_t st) {
     B2S_CHECK(D % 4 == 0 && D <= 1024, "layernorm: D=%d must be a multiple of 4 and <= 1024", D);
-    constexpr bool no_fast = false;             // A/B switch
-    if (!no_fast && (D == 768 || D == 512) && M > 0) {
+    if ((D == 768 || D == 512) && M > 0) {
         if (D == 768) RO_DISPATCH(dtype, hipLaunchKernelGGL((k_ln_fwd_fast<TY, 3>), dim3(cdiv(M, 4)), dim3(256), 0, st, x, gamma, beta, (TY*)y, ldy,
                                                             y32, ldy32, mean, rstd, M, eps, row_len, rows_per_batch));
         else RO_DISPATCH(dtype, hipLaunchKernelGGL((k_ln_fwd_fast<TY, 2>), dim3(cdiv(M, 4)), dim3(256), 0, st, x, gamma, beta, (TY*)y, ldy,
@@ -1263,11 +1239,10 @@ int ro_layernorm_bwd(int dtype, const void* dy, int dy_fp32, int lddy, const flo
                      int M, int D, const int* row_len, int rows_per_batch, hipStream_t st, float* ws, void* dy2, DropCfg drop2,
                      int* defer_nblk, int dx_bf16) {
     B2S_CHECK(D % 4 == 0 && D <= 1024, "layernorm: D=%d must be a multiple of 4 and <= 1024", D);
-    B2S_CHECK(!dx_bf16 || ((D == 768 || D == 512) && (lddy & 3) == 0 && true), "layernorm backward: a bf16 residual gradient needs the D = 512 / 768 kernels");
+    B2S_CHECK(!dx_bf16 || ((D == 768 || D == 512) && (lddy & 3) == 0), "layernorm backward: a bf16 residual gradient needs the D = 512 / 768 kernels");
     int grid = cdiv(M, 4); if (grid > (ws ? RO_LN_WS_ROWS : 512)) grid = ws ? RO_LN_WS_ROWS : 512;
-    constexpr bool no_fast = false;             // A/B switch
     const bool f32 = dy_fp32 || !dtype;
-    if (!no_fast && (D == 768 || D == 512) && M > 0 && (lddy & 3) == 0) {
+    if ((D == 768 || D == 512) && M > 0 && (lddy & 3) == 0) {
         // ~3 rows per wave (the next row's loads fly under the current row's reductions); at most RO_LN_WS_ROWS partial rows
         constexpr int rows_per_wg = 12;
         grid = std::max(1, std::min(cdiv(M, rows_per_wg), ws ? RO_LN_WS_ROWS : 512));
@@ -1470,22 +1445,15 @@ int ro_bn_apply(int dtype, const float* y, const float* mean, const float* rstd,
                 const float* beta, int use_tanh, void* outT, float* out32, const float* add32, int M, int C,
                 DropCfg drop, hipStream_t st) {
     B2S_CHECK(C % 4 == 0, "bn_apply: C=%d must be a multiple of 4", C);
-    constexpr bool scalar = false;               // A/B switch: the round-2 kernels
-    if (!scalar) {
-        BnStat bs = {nullptr, const_cast<float*>(mean), const_cast<float*>(rstd), nullptr, nullptr, nullptr, 0.f, 0.f};
-        dim3 grid(cdiv(C / 4, 64), cdiv(M, 4 * BN_RU));
-        RO_DISPATCH(dtype, hipLaunchKernelGGL((k_bn_apply_v<TY>), grid, dim3(256), 0, st, y, bs, gamma, beta, use_tanh, (TY*)outT, out32, add32, M, C, drop));
-        B2S_LAUNCH_CHECK(); return 0;
-    }
-    RO_DISPATCH(dtype, hipLaunchKernelGGL((k_bn_apply<TY>), dim3(ew_grid((long)M * C / 4)), dim3(256), 0, st, y, mean, rstd,
-                                          gamma, beta, use_tanh, (TY*)outT, out32, add32, M, C, drop));
+    BnStat bs = {nullptr, const_cast<float*>(mean), const_cast<float*>(rstd), nullptr, nullptr, nullptr, 0.f, 0.f};
+    dim3 grid(cdiv(C / 4, 64), cdiv(M, 4 * BN_RU));
+    RO_DISPATCH(dtype, hipLaunchKernelGGL((k_bn_apply_v<TY>), grid, dim3(256), 0, st, y, bs, gamma, beta, use_tanh, (TY*)outT, out32, add32, M, C, drop));
     B2S_LAUNCH_CHECK(); return 0;
 }
 int ro_bn_bwd(int dtype, const void* dout, int dout_fp32, const float* y, const float* mean, const float* rstd,
               const float* gamma, const float* beta, int use_tanh, float* dgamma, float* dbeta, void* dyT, int M,
               int C, DropCfg drop, hipStream_t st) {
-    constexpr bool scalar = false;               // A/B switch: the round-2 kernels
-    if (!scalar && C % 4 == 0) {
+    if (C % 4 == 0) {
         dim3 gv(cdiv(C / 4, 64), cdiv(M, 4 * BN_RU));
 #define B2S_BN_BWD(TD, T) do { \
         hipLaunchKernelGGL((k_bn_bwd_v<TD, T, false>), gv, dim3(256), 0, st, (const TD*)dout, y, mean, rstd, gamma, beta, use_tanh, dgamma, dbeta, (T*)dyT, M, C, drop); \
@@ -1665,9 +1633,5 @@ int ro_mt_param_wire(const MtChunk* chunks, int nchunks, float* wire, const floa
 }
 int ro_mt_zero(const MtChunk* chunks, int nchunks, hipStream_t st) {
     if (nchunks > 0) hipLaunchKernelGGL(k_mt_zero, dim3(nchunks), dim3(256), 0, st, chunks);
-    B2S_LAUNCH_CHECK(); return 0;
-}
-int ro_fill(float* p, float v, long n, hipStream_t st) {
-    hipLaunchKernelGGL(k_fill, dim3(ew_grid(n)), dim3(256), 0, st, p, v, n);
     B2S_LAUNCH_CHECK(); return 0;
 }
