@@ -1,8 +1,11 @@
-"""ctypes binding of libb2s_vocoder.so (C ABI in include/b2s_vocoder.h): batched Griffin-Lim vocoder and mel front end on the GPU.
+"""ctypes binding of libb2s_vocoder.so (C ABI in include/b2s_vocoder.h): batched Griffin-Lim vocoder, mel front end and silence
+splitting / trimming on the GPU.
 
-The reference's utils/audio.py surface (mel2wav, get_spectrograms, save_wav) with librosa 0.6.0 semantics, run as HIP kernels for
-gfx950.  There is no CPU fallback: CPU tensors are refused and a missing library is an error.  Only n_fft 2048, win_length 800,
-hop_length 200 and 80 mels are compiled in; other values are refused by the library with a message naming the supported set.
+The reference's utils/audio.py surface (mel2wav, get_spectrograms, save_wav, trim_silence_intervals) and librosa.effects.split / trim
+with librosa 0.6.0 semantics, run as HIP kernels for gfx950.  There is no CPU fallback: CPU tensors are refused and a missing library
+is an error.  The vocoder and the mel front end have only n_fft 2048, win_length 800, hop_length 200 and 80 mels compiled in; other
+values are refused by the library with a message naming the supported set.  The silence kernels take any frame_length in 2..8192 and
+1 <= hop_length <= frame_length.
 """
 import ctypes as C
 import os
@@ -32,6 +35,9 @@ _PROTOS = {
     "b2s_voc_ws_bytes": (C.c_size_t, [C.POINTER(Params), C.c_int, C.c_int, C.c_int, C.c_int]),
     "b2s_voc_mel2wav": (C.c_int, [C.POINTER(Params), P, P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, C.c_size_t, P]),
     "b2s_voc_wav2mel": (C.c_int, [C.POINTER(Params), P, P, P, C.c_int, C.c_int, C.c_int, P, P, P, C.c_size_t, P]),
+    "b2s_voc_silence_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "b2s_voc_silence_split": (C.c_int, [P, P, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, P, P, P, P, P, P, P, C.c_size_t, P]),
+    "b2s_voc_silence_gather": (C.c_int, [P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P]),
 }
 EXPORTS = sorted(_PROTOS)
 
@@ -211,7 +217,123 @@ def wav2mel_batch(wavs, lengths, hp=None):
     return mels, frames
 
 
+# ---------------------------------------------------------------------------------------------------- silence splitting / trimming
+
+def trim_params(hp=None):
+    """(top_db, frame_length, hop_length) of the reference's trim_silence_intervals: 50 dB, 8 analysis windows, one frame shift."""
+    hp = _hp(hp)
+    return 50, int(hp.sr / 1000 * hp.frame_length_ms) * 8, int(hp.sr / 1000 * hp.frame_shift_ms)
+
+
+def _split_device(wavs, lengths, top_db, frame_length, hop_length, want_flags=False):
+    """One b2s_voc_silence_split call.  Returns a dict of device tensors (intervals [B, NI, 2], n, trim [B, 2], prefix [B, NI],
+    out_lengths [B], flags [B, Fmax] or None) plus the checked wavs tensor and the frame counts; nothing is synchronised."""
+    lib = load()
+    if isinstance(wavs, np.ndarray):
+        wavs = torch.from_numpy(np.ascontiguousarray(wavs, dtype=np.float32)).cuda()
+    if wavs.dim() != 2:
+        raise B2SError("wavs must be [B, Lmax], got %s" % (tuple(wavs.shape),))
+    if wavs.dtype != torch.float32:
+        raise B2SError("wavs must be float32, got %s" % wavs.dtype)
+    ptr(wavs)                                          # refuses CPU / non-contiguous tensors
+    B, Lmax = int(wavs.shape[0]), int(wavs.shape[1])
+    samples = [int(n) for n in lengths]
+    if len(samples) != B:
+        raise B2SError("%d lengths for a batch of %d" % (len(samples), B))
+    if any(n < 2 or n > Lmax for n in samples):
+        raise B2SError("every length must be in 2..Lmax=%d samples (got %s)" % (Lmax, samples))
+    top_db, fl, hop = float(top_db), int(frame_length), int(hop_length)
+    device = wavs.device
+    nbytes = lib.b2s_voc_silence_ws_bytes(B, Lmax, fl, hop)
+    if nbytes == 0:
+        check(1)
+    frames = [1 + (n + 2 * (fl // 2) - fl) // hop for n in samples]
+    fmax = 1 + (Lmax + 2 * (fl // 2) - fl) // hop
+    ni = (fmax + 1) // 2
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    lens = torch.tensor(samples, dtype=torch.int32).to(device)
+    i32 = dict(dtype=torch.int32, device=device)
+    out = {"intervals": torch.empty(B, ni, 2, **i32), "n": torch.empty(B, **i32), "trim": torch.empty(B, 2, **i32),
+           "prefix": torch.empty(B, ni, **i32), "out_lengths": torch.empty(B, **i32),
+           "flags": torch.empty(B, fmax, dtype=torch.uint8, device=device) if want_flags else None,
+           "wavs": wavs, "frames": frames, "shape": (B, Lmax, fl, hop)}
+    check(lib.b2s_voc_silence_split(ptr(wavs), ptr(lens), B, Lmax, top_db, fl, hop, ptr(out["intervals"]), ptr(out["n"]), ptr(out["trim"]),
+                                    ptr(out["prefix"]), ptr(out["out_lengths"]), ptr(out["flags"]) if want_flags else None, ptr(ws),
+                                    ws.numel(), torch.cuda.current_stream(device).cuda_stream))
+    return out
+
+
+def _gather_device(sp):
+    """b2s_voc_silence_gather on the result of _split_device: wav_out [B, Lmax] cuda fp32, zero past out_lengths."""
+    B, Lmax, fl, hop = sp["shape"]
+    wavs = sp["wavs"]
+    wav_out = torch.empty_like(wavs)
+    check(load().b2s_voc_silence_gather(ptr(wavs), B, Lmax, fl, hop, ptr(sp["intervals"]), ptr(sp["n"]), ptr(sp["prefix"]),
+                                        ptr(sp["out_lengths"]), ptr(wav_out), torch.cuda.current_stream(wavs.device).cuda_stream))
+    return wav_out
+
+
+def split_batch(wavs, lengths, top_db=60, frame_length=2048, hop_length=512, return_flags=False):
+    """librosa.effects.split of every utterance of a padded batch [B, Lmax] (cuda tensor or NumPy) with per-utterance sample counts
+    `lengths` (host sequence, every L_b >= 2): a list of int64 [n_b, 2] arrays of [start, end) sample indices.  With return_flags,
+    also the list of per-frame non-silent flags (bool [F_b])."""
+    sp = _split_device(wavs, lengths, top_db, frame_length, hop_length, want_flags=return_flags)
+    n = sp["n"].cpu().numpy()
+    iv = sp["intervals"].cpu().numpy()
+    out = [iv[b, :n[b]].astype(np.int64) for b in range(len(n))]
+    if return_flags:
+        fl = sp["flags"].cpu().numpy()
+        return out, [fl[b, :f].astype(bool) for b, f in enumerate(sp["frames"])]
+    return out
+
+
+def trim_batch(wavs, lengths, top_db=60, frame_length=2048, hop_length=512):
+    """librosa.effects.trim's index of every utterance: int64 [B, 2] (start, end) with the kept signal y[start:end]."""
+    return _split_device(wavs, lengths, top_db, frame_length, hop_length)["trim"].cpu().numpy().astype(np.int64)
+
+
+def remove_silence_batch(wavs, lengths, top_db=60, frame_length=2048, hop_length=512):
+    """np.concatenate([y[l:r] for l, r in librosa.effects.split(y, ...)]) for every utterance of a padded batch: (wav_out [B, Lmax]
+    cuda fp32 with the non-silent intervals concatenated and zeros after, out_lengths as a list).  Kept samples are bit-equal to the
+    input's.  Split and gather run on torch.cuda.current_stream(); reading out_lengths back is the only synchronisation."""
+    sp = _split_device(wavs, lengths, top_db, frame_length, hop_length)
+    wav_out = _gather_device(sp)
+    return wav_out, [int(n) for n in sp["out_lengths"].cpu().numpy()]
+
+
+def trim_silence_intervals_batch(wavs, lengths, hp=None):
+    """The reference's trim_silence_intervals on a padded batch: remove_silence_batch with its parameters (trim_params)."""
+    return remove_silence_batch(wavs, lengths, *trim_params(hp))
+
+
 # ------------------------------------------------------------------------------------------------------ the reference's signatures
+
+def _one_wav(y):
+    y = np.asarray(y, dtype=np.float32)
+    if y.ndim != 1:
+        raise B2SError("wav must be 1-D, got %s" % (y.shape,))
+    return y
+
+
+def trim_silence_intervals(wav, hp=None):
+    """The reference's utils.audio.trim_silence_intervals: waveform (NumPy) -> float32 waveform without its silent intervals."""
+    wav = _one_wav(wav)
+    out, lens = trim_silence_intervals_batch(wav[None], [wav.shape[0]], hp=hp)
+    return out[0, :lens[0]].cpu().numpy()
+
+
+def effects_split(y, top_db=60, frame_length=2048, hop_length=512):
+    """librosa.effects.split(y, top_db, frame_length=..., hop_length=...) for a mono waveform: int64 [n, 2]."""
+    y = _one_wav(y)
+    return split_batch(y[None], [y.shape[0]], top_db, frame_length, hop_length)[0]
+
+
+def effects_trim(y, top_db=60, frame_length=2048, hop_length=512):
+    """librosa.effects.trim: (y[start:end], np.array([start, end]))."""
+    y = _one_wav(y)
+    idx = trim_batch(y[None], [y.shape[0]], top_db, frame_length, hop_length)[0]
+    return y[idx[0]:idx[1]], idx
+
 
 def mel2wav(mel, hp=None):
     """The reference's utils.audio.mel2wav: normalised mel [T, n_mels] (NumPy) -> float32 wav of hop * (T - 1) samples."""

@@ -29,6 +29,10 @@ constexpr int MAG_FRAMES = 16;        // frames per block of k_voc_mag (one read
 
 thread_local std::string g_err;
 
+}  // namespace
+
+// shared with silence.hip (same library): sets the message b2s_voc_last_error() returns, and returns 1
+namespace b2s_voc {
 int fail(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 int fail(const char *fmt, ...) {
     char buf[512];
@@ -39,6 +43,10 @@ int fail(const char *fmt, ...) {
     g_err = buf;
     return 1;
 }
+}  // namespace b2s_voc
+using b2s_voc::fail;
+
+namespace {
 
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 __device__ __forceinline__ float2 cconj(float2 a) { return make_float2(a.x, -a.y); }

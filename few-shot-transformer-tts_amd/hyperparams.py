@@ -10,7 +10,9 @@ performance mode), and the two north-star extensions the reference does not have
 `guided_attention_weight` / `guided_attention_sigma` and `freeze_encoder`; and `vocoder`: "reference" (default: the reference's
 utils.audio Griffin-Lim when importable, else .npy only) or "hip" (the batched GPU vocoder of b2s_hip.vocoder); and `mse_dtw`:
 "reference" (default: the reference's utils.infolog.calculate_mse_dtw, fastdtw on the CPU) or "hip" (eval_batch rebinds it to the
-batched GPU FastDTW of b2s_hip.metrics).
+batched GPU FastDTW of b2s_hip.metrics); and `trim`: "reference" (default: `_trim.wav` through the reference's
+utils.audio.trim_silence_intervals, i.e. librosa, when importable) or "hip" (the batched GPU silence trimming of b2s_hip.vocoder; needs
+vocoder=hip, whose waveforms it trims on the device).
 """
 from utils.hparams import HParams
 
@@ -56,7 +58,7 @@ _SIGNAL = dict(
 
 # MI355X build additions (not in the reference)
 _BUILD = dict(compute_dtype="fp32", guided_attention_weight=0.0, guided_attention_sigma=0.2, freeze_encoder=False,
-              vocoder="reference", mse_dtw="reference")
+              vocoder="reference", mse_dtw="reference", trim="reference")
 
 _GROUPS = (_MODEL, _OPTIMISER, _BATCHING, _EVAL, _SIGNAL, _BUILD)
 assert sum(len(g) for g in _GROUPS) == len(set().union(*_GROUPS)), "a hyper-parameter is defined in two groups"

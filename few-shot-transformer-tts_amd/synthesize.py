@@ -242,8 +242,10 @@ def save_eval_results(names, mel_pre, mel_aft, alignments, input_lengths, genera
     is logged and skipped, as in the reference; samples are written by a small thread pool.
 
     With hp.vocoder == "hip" the wavs come from the batched GPU Griffin-Lim (b2s_hip.vocoder): every sample with at least 2 frames
-    is vocoded in one call before the pool starts and written with the package's save_wav; `_trim.wav` needs the reference's
-    trim_silence_intervals (librosa).  If the vocoder fails as a whole, that is logged and the .npy files are still written."""
+    is vocoded in one call before the pool starts and written with the package's save_wav.  `_trim.wav` needs the reference's
+    trim_silence_intervals (librosa) with hp.trim == "reference"; with hp.trim == "hip" (which needs vocoder=hip) the vocoder's output
+    stays on the device, the whole batch is trimmed there in one call (b2s_hip.vocoder.trim_silence_intervals_batch) and `_trim.wav`
+    is written from that.  If the vocoder fails as a whole, that is logged and the .npy files are still written."""
     import threading
     import traceback
     from concurrent.futures import ThreadPoolExecutor
@@ -257,12 +259,19 @@ def save_eval_results(names, mel_pre, mel_aft, alignments, input_lengths, genera
         from utils.infolog import plot_attn, plot_mel
     except Exception:                       # matplotlib / fastdtw are optional
         plot_attn = plot_mel = None
+    if hp.trim not in ("reference", "hip"):
+        raise ValueError("unknown trim %r (expected 'reference' or 'hip')" % (hp.trim,))
+    if hp.trim == "hip" and hp.vocoder == "reference":
+        raise ValueError("trim=hip needs vocoder=hip: it trims the GPU vocoder's waveforms on the device")
     os.makedirs(output_dir, exist_ok=True)
-    gpu_wavs = None
+    gpu_wavs = gpu_trimmed = None
     if hp.vocoder == "hip":
         mel2wav = None                      # the reference's CPU vocoder is not used
-        gpu_wavs, save_wav = _vocode_batch_hip(names, mel_aft, generated_lengths)
-        if save_trimmed_wave and gpu_wavs and trim_silence_intervals is None:
+        gpu_wavs, gpu_trimmed, save_wav = _vocode_batch_hip(names, mel_aft, generated_lengths,
+                                                            trim=save_trimmed_wave and hp.trim == "hip")
+        if hp.trim == "hip":
+            trim_silence_intervals = None   # nor its trimming
+        elif save_trimmed_wave and gpu_wavs and trim_silence_intervals is None:
             logging.warning("vocoder=hip: trimmed waves need the reference's utils.audio.trim_silence_intervals (librosa); "
                             "writing untrimmed waves only")
     elif hp.vocoder != "reference":
@@ -278,7 +287,9 @@ def save_eval_results(names, mel_pre, mel_aft, alignments, input_lengths, genera
                     raise ValueError("sample %s has %d frames; the vocoder needs at least 2" % (name, n))
                 wav = gpu_wavs[i]
                 save_wav(wav, os.path.join(output_dir, '%s.wav' % name))
-                if save_trimmed_wave and trim_silence_intervals is not None:
+                if save_trimmed_wave and gpu_trimmed is not None:
+                    save_wav(gpu_trimmed[i], os.path.join(output_dir, '%s_trim.wav' % name))
+                elif save_trimmed_wave and trim_silence_intervals is not None:
                     save_wav(trim_silence_intervals(wav), os.path.join(output_dir, '%s_trim.wav' % name))
             elif mel2wav is not None:
                 wav = mel2wav(mel)
@@ -300,9 +311,11 @@ def save_eval_results(names, mel_pre, mel_aft, alignments, input_lengths, genera
     logging.info('[%s] Finished saving evals in %.2f secs: ' % (threading.current_thread().name, time.time() - tic) + str(names))
 
 
-def _vocode_batch_hip(names, mel_aft, generated_lengths):
-    """vocoder=hip: one mel2wav_batch call for every sample with a valid length (>= 2 frames).  Returns ({sample index: wav},
-    the package's save_wav), or (None, None) after a failure of the whole call, which is logged."""
+def _vocode_batch_hip(names, mel_aft, generated_lengths, trim=False):
+    """vocoder=hip: one mel2wav_batch call for every sample with a valid length (>= 2 frames); with `trim` (trim=hip) its output stays
+    on the device and one trim_silence_intervals_batch call trims the whole batch.  Returns ({sample index: wav}, {sample index:
+    trimmed wav} or None without `trim`, the package's save_wav), or (None, None, None) after a failure of the whole call, which is
+    logged."""
     import traceback
 
     import numpy as np
@@ -317,15 +330,20 @@ def _vocode_batch_hip(names, mel_aft, generated_lengths):
             if 2 <= n <= np.asarray(mel_aft[i]).shape[0]:
                 ok.append((i, n))
         if not ok:
-            return {}, vocoder.save_wav
+            return {}, ({} if trim else None), vocoder.save_wav
         tmax = max(n for _, n in ok)
         mels = np.zeros([len(ok), tmax, hp.num_mels], dtype=np.float32)
         for j, (i, n) in enumerate(ok):
             mels[j, :n] = np.asarray(mel_aft[i])[:n]
-        wav, lens = vocoder.mel2wav_batch(mels, [n for _, n in ok])
-        wav = wav.cpu().numpy()
-        return {i: wav[j, :lens[j]] for j, (i, _) in enumerate(ok)}, vocoder.save_wav
+        wav_d, lens = vocoder.mel2wav_batch(mels, [n for _, n in ok])
+        trimmed = None
+        if trim:
+            trim_d, trim_lens = vocoder.trim_silence_intervals_batch(wav_d, lens)
+            trim_h = trim_d.cpu().numpy()
+            trimmed = {i: trim_h[j, :trim_lens[j]] for j, (i, _) in enumerate(ok)}
+        wav = wav_d.cpu().numpy()
+        return {i: wav[j, :lens[j]] for j, (i, _) in enumerate(ok)}, trimmed, vocoder.save_wav
     except Exception:
         logging.error('GPU vocoder failed for ' + str(list(names)) + '; writing mel .npy files only')
         logging.error(traceback.format_exc())
-        return None, None
+        return None, None, None

@@ -1,4 +1,5 @@
-/* C ABI of libb2s_vocoder.so: batched Griffin-Lim vocoder (mel -> wav) and mel front end (wav -> mel) for gfx950.
+/* C ABI of libb2s_vocoder.so: batched Griffin-Lim vocoder (mel -> wav), mel front end (wav -> mel) and silence splitting / trimming
+ * (the b2s_voc_silence_* calls at the end, which take their own parameters instead of B2SVocParams) for gfx950.
  *
  * The reference's utils/audio.py (librosa 0.6.0 semantics) on the GPU, fp32 throughout.  Only n_fft 2048, win 800, hop 200 and
  * 80 mels are compiled in; any other value is refused with an error naming the supported set.  Utterances are packed ragged:
@@ -39,6 +40,25 @@ int b2s_voc_mel2wav(const B2SVocParams *p, const float *mels, const int32_t *fra
  * written, the rest left untouched).  basis = mel basis [n_mels, 1 + n_fft / 2] fp32. */
 int b2s_voc_wav2mel(const B2SVocParams *p, const float *wav, const int32_t *lengths, const int32_t *frame_offsets, int B, int Lmax,
                     int total_frames, const float *basis, float *mels_out, void *ws, size_t ws_bytes, void *stream);
+
+/* Silence splitting / trimming (librosa 0.6.0 effects.split / effects.trim semantics; csrc/vocoder/silence.hip).  Ragged batch:
+ * wav [B, Lmax] fp32, lengths [B] int32 samples on the device, every L_b in 2..Lmax (a length outside is clamped, never read past).
+ * frame_length in 2..8192, 1 <= hop_length <= frame_length, top_db > 0.  With Fmax = 1 + (Lmax + 2 * (frame_length / 2) -
+ * frame_length) / hop_length frames at most and NI = (Fmax + 1) / 2 intervals at most:
+ *   intervals [B, NI, 2] int32   [start, end) in samples, rows i < n_intervals[b] written
+ *   n_intervals [B], trim_index [B, 2] (effects.trim's start, end), out_lengths [B] = kept samples
+ *   prefix [B, NI]               exclusive prefix sum of the interval lengths (where interval i starts in the gathered output)
+ *   flags [B, Fmax] uint8        the non-silent flag of every frame f < F_b; may be NULL */
+size_t b2s_voc_silence_ws_bytes(int B, int Lmax, int frame_length, int hop_length);   /* 0 on an argument error (message set) */
+
+int b2s_voc_silence_split(const float *wav, const int32_t *lengths, int B, int Lmax, double top_db, int frame_length, int hop_length,
+                          int32_t *intervals, int32_t *n_intervals, int32_t *trim_index, int32_t *prefix, int32_t *out_lengths,
+                          uint8_t *flags, void *ws, size_t ws_bytes, void *stream);
+
+/* wav_out [B, Lmax] fp32 = the samples of the intervals of b2s_voc_silence_split (same B, Lmax, frame_length, hop_length), concatenated,
+ * zero from out_lengths[b] on.  A pure copy: kept samples are bit-equal to the input's. */
+int b2s_voc_silence_gather(const float *wav, int B, int Lmax, int frame_length, int hop_length, const int32_t *intervals,
+                           const int32_t *n_intervals, const int32_t *prefix, const int32_t *out_lengths, float *wav_out, void *stream);
 
 #ifdef __cplusplus
 }
