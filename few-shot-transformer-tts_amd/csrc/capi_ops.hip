@@ -40,6 +40,18 @@ extern "C" int b2s_gemm(const b2s_gemm_desc* d, const void* A, const void* B, vo
     g.epi.residual = residual; g.epi.ldr = d->ldc;
     g.epi.row_len = row_len; g.epi.rows_per_batch = d->rows_per_batch > 0 ? d->rows_per_batch : 1;
     g.epi.conv_dw_cin = d->conv_dw_cin;
+    if (d->conv_dw_cin > 0 && d->conv_T > 0 && d->conv_cin_a == 0) {
+        // conv weight gradient on the UN-gathered conv input: A = dy [K = B conv_T token rows][M = cout], B = x [K][conv_dw_cin], N = 5 cin;
+        // the taps are row shifts inside every utterance's conv_T rows, valid input rows [0, conv_len[b])   (gemm.h: b2s_gemm_conv_dw_launch)
+        B2S_CHECK(d->dtype == 1 && d->trans_a && d->trans_b && g.batch == 1 && d->c_fp32 && d->alpha == 1.f && !bias && !residual && !row_len && !d->relu &&
+                  d->drop_p == 0.f, "conv dW on token rows: bf16 TN form, fp32 output, linear epilogue");
+        B2S_CHECK(d->N == 5 * d->conv_dw_cin && d->K % d->conv_T == 0, "conv dW on token rows: N = %d must be 5 cin (cin = %d), K = %d a multiple of T = %d",
+                  d->N, d->conv_dw_cin, d->K, d->conv_T);
+        GemmArgs w;
+        w.A.p = A; w.A.ld = d->lda; w.B.p = B; w.B.ld = d->ldb; w.M = d->M; w.N = d->conv_dw_cin; w.K = d->K;
+        w.C = C; w.c_fp32 = 1; w.ldc = d->ldc; w.epi.accumulate = d->accumulate;
+        return b2s_gemm_conv_dw_launch(&w, 1, conv_len, d->K / d->conv_T, d->conv_T, S_(stream));
+    }
     return b2s_gemm_launch(g, d->dtype, d->trans_a != 0, d->trans_b != 0, S_(stream));
 }
 extern "C" int b2s_gemm_splitk(const b2s_gemm_desc* d, int splitk, const void* A, const void* B, float* C, float* ws, size_t ws_floats,

@@ -687,7 +687,7 @@ void plan_decoder(const b2s_model* m, b2s_ctx& c, Arena& a, Scratch& sc, std::ve
     if (m->kv_cat) { sc.dctx_x = a.T(M * D, esz); sc.dsum_x = a.f32((long)B * H * T); }
 }
 
-struct PostScratch { std::vector<void*> du, dy; float* stat; int stat_stride; void* col = nullptr; };       // stat: [n layers][2 maxc] column sums (zeroed once per forward)
+struct PostScratch { std::vector<void*> du, dy; float* stat; int stat_stride; };       // stat: [n layers][2 maxc] column sums (zeroed once per forward)
 void plan_postnet(const b2s_model* m, b2s_ctx& c, Arena& a, PostScratch& ps) {
     const b2s_config& cf = m->cfg;
     const long M = (long)c.B * c.T;
@@ -711,11 +711,6 @@ void plan_postnet(const b2s_model* m, b2s_ctx& c, Arena& a, PostScratch& ps) {
     for (int i = 0; i < n; ++i) ps.dy[i] = a.T(M * (i == n - 1 ? cf.num_mels : cf.postnet_hidden), esz);
     ps.stat_stride = 2 * maxc;
     ps.stat = a.f32((long)n * ps.stat_stride);
-    // bf16: the gathered [tokens, 5 taps x channels] operand of one conv weight gradient, written out (41.7 MB at the default sizes) so
-    // that the weight-gradient GEMM reads a plain matrix: with the gather inside the kernel its MFMA waves issue the loads themselves and
-    // compute two divisions per 16-byte chunk (60-113 us per layer against 12 + ~40 with the copy); one buffer, reused layer after layer
-    // on the second stream
-    if (m->dtype == 1) ps.col = a.T(M * 5 * maxc, esz);
 }
 
 int check_bound(const b2s_model* m) {
@@ -2016,10 +2011,13 @@ extern "C" int b2s_postnet_backward(b2s_model* m, b2s_ctx* c, const float* d_out
     b2s_ctx tmp; tmp.B = B; tmp.T = T;
     PostScratch ps;
     plan_postnet(m, tmp, a, ps);
-    // The conv weight gradients (5 split-K GEMMs over all tokens + their slab reductions, ~0.3 ms) are not on the path to d_inputs:
-    // with a second stream they are queued and run there after the pass, behind one event, while the caller's decoder backward
-    // proceeds on the main stream.
-    std::vector<GemmArgs> dws;
+    // The conv weight gradients are not on the path to d_inputs: with a second stream they are queued and run there after the pass,
+    // behind one event, while the caller's decoder backward proceeds on the main stream.
+    // bf16, channel counts that are multiples of 8 (`segs`): all layers in ONE grouped launch whose K walk is cut into per-utterance
+    // segments -- a filter tap is a row shift between dy and the saved conv input, so nothing is gathered, copied or slab-reduced
+    // (gemm.h: b2s_gemm_conv_dw_launch; the lengths are read on the device, so the path is the same with and without a host copy).
+    // fp32, or other channel counts (`dws`): one gather GEMM per layer.
+    std::vector<GemmArgs> dws, segs;
     for (int i = n - 1; i >= 0; --i) {
         const int cin = i == 0 ? cf.num_mels : cf.postnet_hidden, cout = i == n - 1 ? cf.num_mels : cf.postnet_hidden;
         const std::string q = "postnet.batchnorm_layers." + std::to_string(i) + ".";
@@ -2028,7 +2026,14 @@ extern "C" int b2s_postnet_backward(b2s_model* m, b2s_ctx* c, const float* d_out
         void* dy = ps.dy[i];
         B2S_TRY(ro_bn_bwd(dt, dout, i == n - 1 ? 1 : 0, c->y[i], c->bn_mean[i], c->bn_rstd[i], m->P(q + "weight"), m->P(q + "bias"),
                           i < n - 1 ? 1 : 0, m->G(q + "weight"), m->G(q + "bias"), dy, (int)M, cout, d, st));
-        {   // dW[co, ci, j] = sum_m dy[m, co] * xg[m, j*cin + ci]
+        if (dt == 1 && cin % 8 == 0 && cout % 8 == 0) {   // dW[co, ci, j] = sum_b sum_t dy[b T + t, co] * u[b T + t + j - 2, ci]
+            GemmArgs g;
+            g.A.p = dy; g.A.ld = cout; g.B.p = c->u[i]; g.B.ld = cin;
+            g.M = cout; g.N = cin; g.K = (int)M;
+            g.C = m->G("postnet.conv_layers." + std::to_string(i) + ".weight"); g.c_fp32 = 1; g.ldc = 5 * cin;
+            g.epi.accumulate = 1;
+            segs.push_back(g);
+        } else {   // dW[co, ci, j] = sum_m dy[m, co] * xg[m, j*cin + ci]
             GemmArgs g;
             g.A.p = dy; g.A.ld = cout; g.A.R = (int)M; g.A.C = cout;
             g.B.p = c->u[i]; g.B.ld = cin; g.B.R = (int)M; g.B.C = 5 * cin; g.B.g_cin = cin; g.B.g_T = T; g.B.g_len = c->tgt_len;
@@ -2049,17 +2054,18 @@ extern "C" int b2s_postnet_backward(b2s_model* m, b2s_ctx* c, const float* d_out
             B2S_TRY(b2s_gemm_launch(g, dt, false, false, st));
         }
     }
-    if (!dws.empty()) {
+    auto launch_segs = [&](hipStream_t s) -> int {
+        for (size_t i = 0; i < segs.size(); i += B2S_MAX_GROUP)
+            B2S_TRY(b2s_gemm_conv_dw_launch(segs.data() + i, (int)std::min<size_t>(B2S_MAX_GROUP, segs.size() - i), c->tgt_len, B, T, s));
+        return 0;
+    };
+    if (!m->aux) B2S_TRY(launch_segs(st));
+    else if (!dws.empty() || !segs.empty()) {
         hipEvent_t ready = m->next_event();
         B2S_HIP(hipEventRecord(ready, st));
         B2S_HIP(hipStreamWaitEvent(m->aux, ready, 0));
-        for (GemmArgs& g : dws) {
-            if (ps.col && g.B.g_cin % 8 == 0) {
-                B2S_TRY(ro_im2col5(dt, g.B.p, g.B.g_len, g.B.g_T, g.B.g_cin, ps.col, (long)g.B.R, m->aux));
-                g.B.p = ps.col; g.B.ld = 5 * g.B.g_cin; g.B.g_cin = 0; g.B.g_T = 0; g.B.g_len = nullptr;
-            }
-            m->set_ws(g, m->aux); B2S_TRY(b2s_gemm_launch(g, dt, true, true, m->aux));
-        }
+        for (GemmArgs& g : dws) { m->set_ws(g, m->aux); B2S_TRY(b2s_gemm_launch(g, dt, true, true, m->aux)); }
+        B2S_TRY(launch_segs(m->aux));
         hipEvent_t done = m->next_event();
         B2S_HIP(hipEventRecord(done, m->aux));
         m->aux_dirty = true;

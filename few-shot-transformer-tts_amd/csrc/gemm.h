@@ -73,8 +73,17 @@ int b2s_gemm_glds256_launch(const GemmArgs& g, bool ta, bool tb, const bf16_t* z
 int b2s_splitk_reduce_launch(const float* ws, float* dst, int M, int N, int ldc, int splitk, int conv_dw_cin, hipStream_t stream);
 // up to B2S_MAX_GROUP weight-gradient problems (TN form, fp32 accumulate, no split-K) in one launch
 #define B2S_MAX_GROUP 8
-struct b2s_gemm_group { int n; int order; int tile0[B2S_MAX_GROUP + 1]; GemmArgs p[B2S_MAX_GROUP]; };      // order: 1 = XCD-contiguous over the whole list
+// K segments (conv weight gradients, seg_n > 0): the K walk of every work item is cut into seg_n segments, one per utterance b, each with its own
+// A row base, B row base and K length (derived in the kernel from the row shift of the work item's filter tap, see conv_seg() in gemm_glds256.hip)
+struct b2s_gemm_group { int n; int order; int tile0[B2S_MAX_GROUP + 1]; GemmArgs p[B2S_MAX_GROUP];       // order: 1 = XCD-contiguous over the whole list
+                        const int* seg_len; int seg_n, seg_T; };
 int b2s_gemm_glds256_grouped_launch(const GemmArgs* probs, int n, const bf16_t* zero, hipStream_t stream);
+// Weight gradients of up to B2S_MAX_GROUP Conv1d(k = 5, pad = 2) layers over the same [B][T] token rows in one launch, without a gathered operand:
+//   C[co][ci*5 + j] (+)= sum_b sum_t dy[b*T + t][co] * x[b*T + t + j - 2][ci]   over 0 <= t < T, 0 <= t + j - 2 < min(len[b], T)   (len = nullptr: T)
+// Problem i: A = dy (A.p, A.ld, A.C = M = cout), B = x (B.p, B.ld, B.C = N = cin), C fp32 [cout][ldc >= 5 cin], epi.accumulate; cin, cout and the
+// leading dimensions multiples of 8.  len is DEVICE memory (no host copy is needed: a workgroup reads the seg_n lengths itself).
+int b2s_gemm_glds256_conv_dw_launch(const GemmArgs* probs, int n, const int* len, int B, int T, const bf16_t* zero, hipStream_t stream);
+int b2s_gemm_conv_dw_launch(const GemmArgs* probs, int n, const int* len, int B, int T, hipStream_t stream);      // gemm.hip: + optional timing record
 // 256 zero bytes in device memory, written once at first use and immutable afterwards (source of the out-of-bounds chunks of
 // the LDS-DMA loads); the only process-wide device object of the GEMM layer
 const bf16_t* b2s_gemm_zero_page();

@@ -289,6 +289,22 @@ int b2s_gemm_grouped_launch(const GemmArgs* probs, int n, hipStream_t stream) {
     { std::lock_guard<std::mutex> lock(g_prof_mu); g_prof.push_back(r); }
     return rc;
 }
+// conv weight gradients on per-utterance K segments (gemm_glds256.hip), timing record as variant 16
+int b2s_gemm_conv_dw_launch(const GemmArgs* probs, int n, const int* len, int B, int T, hipStream_t stream) {
+    const bf16_t* zero = b2s_gemm_zero_page();
+    if (!zero) return 1;               // (b2s_fail has recorded the HIP error)
+    if (!g_prof_on) return b2s_gemm_glds256_conv_dw_launch(probs, n, len, B, T, zero, stream);
+    ProfRec r;
+    B2S_HIP(hipEventCreate(&r.a)); B2S_HIP(hipEventCreate(&r.b));
+    r.variant = 16; r.flops = 0.0;
+    for (int i = 0; i < n; ++i) r.flops += 2.0 * probs[i].M * 5.0 * probs[i].N * (double)B * T;
+    r.M = probs[0].M; r.N = 5 * probs[0].N; r.K = B * T; r.batch = n; r.splitk = 1;
+    B2S_HIP(hipEventRecord(r.a, stream));
+    int rc = b2s_gemm_glds256_conv_dw_launch(probs, n, len, B, T, zero, stream);
+    B2S_HIP(hipEventRecord(r.b, stream));
+    { std::lock_guard<std::mutex> lock(g_prof_mu); g_prof.push_back(r); }
+    return rc;
+}
 static int gemm_launch_inner(const GemmArgs& g, int dtype, bool ta, bool tb, hipStream_t stream) {
     const int ve = dtype ? 8 : 4;
     B2S_CHECK(g.M > 0 && g.N > 0 && g.K > 0 && g.batch > 0 && g.batch_inner > 0, "gemm: bad shape M=%d N=%d K=%d batch=%d",

@@ -109,8 +109,24 @@ __device__ inline int xcd_tile_id(int orig, int nwg) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
 }
 
-template <bool TA, bool TB, int GATHER, int NB, int MW = 4>
-__device__ __forceinline__ void gemm256_body(GemmArgs g, const bf16_t* zero, float* splitk_ws, int bx, int by, int bz) {
+// K segments of a conv weight-gradient work item (SEG bodies: TN form, dW[co][ci] of ONE filter tap j, shift = j - 2):
+//     dW_j[co][ci] = sum_b sum_t dy[b T + t][co] * x[b T + t + shift][ci]
+// Segment rule.  The reference zero-pads the conv INPUT outside [0, len_b) and sums over every row t of the conv OUTPUT gradient: dy is NOT zero on
+// the rows t >= len_b (the BatchNorm backward, k_bn_bwd_v, subtracts batch means on all B T rows, and the forward took its statistics over all of them),
+// so those rows of dy stay in the sum as long as the input row they meet is a real one.  Utterance b therefore contributes the rows
+//     t0 = max(0, -shift)  <=  t  <  t1 = min(T, len_b - shift)        (len_b clamped to [0, T]; empty when t1 <= t0)
+// of dy, against the rows t + shift of x, which lie in [0, len_b): both ranges are inside utterance b's T rows of their buffers, nothing is
+// gathered or masked, and rows of x at or beyond len_b are never read (they need not hold zeros).
+struct ConvSeg { const int* len; int n, T, shift; };
+__device__ __forceinline__ void conv_seg(const ConvSeg& sg, int b, int& row, int& klen) {
+    const int len = sg.len ? min(max(sg.len[b], 0), sg.T) : sg.T;
+    const int t0 = max(0, -sg.shift), t1 = min(sg.T, len - sg.shift);
+    row = b * sg.T + t0; klen = max(t1 - t0, 0);
+}
+
+template <bool TA, bool TB, int GATHER, int NB, int MW = 4, bool SEG = false>
+__device__ __forceinline__ void gemm256_body(GemmArgs g, const bf16_t* zero, float* splitk_ws, int bx, int by, int bz, const ConvSeg sg = ConvSeg{nullptr, 0, 0, 0}) {
+    static_assert(!SEG || (TA && TB && GATHER == 0 && MW == 4 && NPROD > 0), "K segments: the producer-wave TN form only");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     // conv-gather operands keep the DMA issue on the MFMA waves: their per-chunk address arithmetic (two divisions, a length
     // lookup) serialised on 4 producer waves costs more than the blocking issue does (60 -> 84 us on the postnet GEMMs)
@@ -189,24 +205,64 @@ __device__ __forceinline__ void gemm256_body(GemmArgs g, const bf16_t* zero, flo
         }
     }
     const int g_spt = GF ? g.A.g_cin / BK : 1;                           // K steps per filter tap
-    const bool fast_ok = GATHER != 1 && nfull > 0 && (TA ? (g.A.C >= 8 && (g.A.C & 7) == 0) : true) && (TB ? (g.B.C >= 8 && (g.B.C & 7) == 0) : true) &&
+    const bool fast_ok = GATHER != 1 && (SEG || nfull > 0) && (TA ? (g.A.C >= 8 && (g.A.C & 7) == 0) : true) && (TB ? (g.B.C >= 8 && (g.B.C & 7) == 0) : true) &&
                          (TA ? (long)g.A.R * g.A.ld : (long)g.A.R * g.A.ld) < (1L << 30) && (long)g.B.R * g.B.ld < (1L << 30);
     // B instructions 12..15 of a 96-column tile would fill image rows no wave reads: waves 6, 7 skip them (4 DMAs per step)
     // (K-contiguous B only: a reduction-major B instruction covers 4 k rows x all 128 columns, every one is needed)
     const bool b_active0 = NP || NB == 4 || TB || wave * 2 + 0 < 12, b_active1 = NP || NB == 4 || TB || wave * 2 + 1 < 12;
     const bool six = b_active0 && b_active1;                             // this wave issues 6 (else 4) DMA instructions per step
 
-    const int nk_all = (g.K + BK - 1) / BK;
+    // K segments: the K walk is the concatenation of the segments' K steps, every segment rounded up to whole steps (its last step is zero-filled
+    // past the segment's end exactly as the last step of an unaligned K is); a split of the walk is balanced by steps, i.e. by segment rows
+    int nk_all = (g.K + BK - 1) / BK;
+    if (SEG) {
+        nk_all = 0;
+        for (int b = 0; b < sg.n; ++b) { int row, klen; conv_seg(sg, b, row, klen); nk_all += (klen + BK - 1) / BK; }
+    }
+    int sg_b = -1, sg_first = 0, sg_steps = 0, sg_klen = 0, sg_row = 0;        // the issuing wave's position in the segment list (kt only grows)
     const int per = (nk_all + g.splitk - 1) / g.splitk;
     const int kt0 = ksplit * per;
     const int kt_end = min(nk_all, kt0 + per);
     const int nk = kt_end - kt0;
-    if (nk <= 0) return;
+    if (!SEG && nk <= 0) return;          // (K segments may all be empty: the tile still stores / accumulates its zeros)
 
     // Always exactly 6 DMA instructions per wave and stage (stages past the end fetch the zero page into a slot nobody
     // reads again): the in-flight count is a compile-time constant and the counted waits below never drain the queue.
     auto issue = [&](int kt, int slot) {
         unsigned char* sbase = smem_raw + slot * STG;
+        if (SEG) {
+            // (called for kt0 <= kt < kt_end <= nk_all only, so a segment that holds step kt exists)
+            while (kt >= sg_first + sg_steps && sg_b + 1 < sg.n) {
+                sg_first += sg_steps; ++sg_b;
+                conv_seg(sg, sg_b, sg_row, sg_klen);
+                sg_steps = (sg_klen + BK - 1) / BK;
+            }
+            const int ks = kt - sg_first, left = sg_klen - ks * BK;             // rows of the segment from this step on
+            const long ra = sg_row + ks * BK, rb = ra + sg.shift;                // first dy row / first x row of the step
+            if (fast_ok && left >= BK) {
+                const char* sa = reinterpret_cast<const char*>(Ab) + ra * g.A.ld * 2;
+                const char* sb = reinterpret_cast<const char*>(Bb) + rb * g.B.ld * 2;
+#pragma unroll
+                for (int i = 0; i < NIA; ++i)
+                    __builtin_amdgcn_global_load_lds((gptr_t)(sa + goffA[i]), (lptr_t)(sbase + (ia0 + i) * 1024), 16, 0, B2S_DMA_AUX);
+#pragma unroll
+                for (int i = 0; i < NIB; ++i)
+                    __builtin_amdgcn_global_load_lds((gptr_t)(sb + goffB[i]), (lptr_t)(sbase + A_B + (ib0 + i) * 1024), 16, 0, B2S_DMA_AUX);
+                return;
+            }
+            // last step of a segment: rows at or past its end come from the zero page (never from the neighbouring utterance)
+#pragma unroll
+            for (int i = 0; i < NIA; ++i) {
+                const bf16_t* sa = (ka[i] >= 0 && ka[i] < left) ? pa[i] + ra * g.A.ld : zero;
+                __builtin_amdgcn_global_load_lds((gptr_t)sa, (lptr_t)(sbase + (ia0 + i) * 1024), 16, 0, B2S_DMA_AUX);
+            }
+#pragma unroll
+            for (int i = 0; i < NIB; ++i) {
+                const bf16_t* sb = (kb_[i] >= 0 && kb_[i] < left) ? pb[i] + rb * g.B.ld : zero;
+                __builtin_amdgcn_global_load_lds((gptr_t)sb, (lptr_t)(sbase + A_B + (ib0 + i) * 1024), 16, 0, B2S_DMA_AUX);
+            }
+            return;
+        }
         if (fast_ok && (kt < nfull || kt >= kt_end)) {                   // (steps past the end re-fetch the last full one: never consumed)
             const long ks = min(kt, nfull - 1);
             const char* sa = reinterpret_cast<const char*>(Ab) + ks * stepA * 2;
@@ -401,7 +457,9 @@ __global__ __launch_bounds__(nthreads_of(GATHER, MW), 1) void gemm_glds256_kerne
 // Grouped weight-gradient launch: up to B2S_MAX_GROUP independent dW = dY^T X problems (TN form, fp32 accumulate) in one
 // grid.  A training layer's weight gradients are 18 .. 72 tiles each -- far too few to fill 256 CUs one at a time, which
 // is what split-K + a slab-reduce kernel used to paper over; together they are ~290 tiles with the full 8148-deep K.
-template <int NB>
+// SEG (conv weight gradients): problem p is one conv layer, its tile list is [cout / 256 row panels][5 taps x cin / 128 column panels]; a tile
+// computes dW of one tap over the K segments of conv_seg() and stores column ci at ci*5 + tap.
+template <int NB, bool SEG = false>
 __global__ __launch_bounds__(nthreads_of(false), 1) void gemm_glds256_grouped_kernel(b2s_gemm_group grp, const bf16_t* zero) {
     // Workgroup i runs on XCD i % 8.  The list is walked in launch order (problem ranges tile0[]), so every XCD gets an equal
     // share of every problem -- a globally XCD-contiguous order handed all 36 short tiles of a decoder layer to one XCD and
@@ -430,7 +488,8 @@ __global__ __launch_bounds__(nthreads_of(false), 1) void gemm_glds256_grouped_ke
         }
         local = before + (i - (s0 + ((xcd - s0) & 7))) / 8;
     }
-    const int tiles_n = (grp.p[p].N + NB * 32 - 1) / (NB * 32), tiles_m = (grp.p[p].M + BM - 1) / BM;
+    const int tiles_tap = (grp.p[p].N + NB * 32 - 1) / (NB * 32);              // column panels (of one tap)
+    const int tiles_n = SEG ? 5 * tiles_tap : tiles_tap, tiles_m = (grp.p[p].M + BM - 1) / BM;
     // K split over `splitk` workgroups per output tile (fp32 atomic accumulate; with two halves added to a zeroed gradient the result does
     // not depend on their order): the K parts of a tile are adjacent in the XCD's list, so they share its A / B panels' neighbours in L2
     const int sk = grp.p[p].splitk, t = local / sk, bz = local - t * sk;
@@ -439,6 +498,14 @@ __global__ __launch_bounds__(nthreads_of(false), 1) void gemm_glds256_grouped_ke
     // instead of 2 x 24
     if (grp.order == 1 && tiles_n > 8) { bx = t / tiles_m; by = t - bx * tiles_m; }
     else { by = t / tiles_n; bx = t - by * tiles_n; }
+    if constexpr (SEG) {
+        GemmArgs g = grp.p[p];
+        const int j = bx / tiles_tap;
+        g.C = reinterpret_cast<float*>(g.C) + j;                                // epilogue: column ci -> ci*5 (conv_dw_cin = cin), + tap
+        const ConvSeg sg = {grp.seg_len, grp.seg_n, grp.seg_T, j - 2};
+        gemm256_body<true, true, 0, NB, 4, true>(g, zero, nullptr, bx - j * tiles_tap, by, 0, sg);
+        return;
+    }
     gemm256_body<true, true, 0, NB>(grp.p[p], zero, nullptr, bx, by, bz);
 }
 
@@ -933,6 +1000,7 @@ int b2s_gemm_glds256_grouped_launch(const GemmArgs* probs, int n, const bf16_t* 
         tiles += cdiv(g.M, t256::BM) * cdiv(g.N, 128);
     }
     grp.tile0[n] = tiles;
+    grp.seg_len = nullptr; grp.seg_n = 0; grp.seg_T = 0;
     constexpr size_t smem = (size_t)t256::NSTAGE * t256::STAGE_BYTES;
     static std::once_flag attr_once;
     static hipError_t attr_err = hipSuccess;
@@ -942,6 +1010,44 @@ int b2s_gemm_glds256_grouped_launch(const GemmArgs* probs, int n, const bf16_t* 
     });
     B2S_HIP(attr_err);
     hipLaunchKernelGGL((t256::gemm_glds256_grouped_kernel<4>), dim3(tiles), dim3(t256::nthreads_of(false)), smem, stream, grp, zero);
+    B2S_LAUNCH_CHECK();
+    return 0;
+}
+
+int b2s_gemm_glds256_conv_dw_launch(const GemmArgs* probs, int n, const int* len, int B, int T, const bf16_t* zero, hipStream_t stream) {
+    B2S_CHECK(n >= 1 && n <= B2S_MAX_GROUP && B > 0 && T > 0 && (long)B * T < (1L << 30), "conv dW: %d layers (max %d), B = %d, T = %d", n, B2S_MAX_GROUP, B, T);
+    b2s_gemm_group grp;
+    grp.n = n; grp.order = 1;
+    grp.seg_len = len; grp.seg_n = B; grp.seg_T = T;
+    // One workgroup per (row panel, tap, column panel) walks the whole K: the five postnet layers of the training step are 150 tiles, one round
+    // on 256 CUs, and every element of the gradient is written by exactly one workgroup (no split-K partial sums, no atomics: deterministic)
+    int tiles = 0;
+    for (int k = 0; k < n; ++k) {
+        GemmArgs g = probs[k];
+        B2S_CHECK(g.batch == 1 && g.c_fp32 && g.A.p && g.B.p && g.C && g.A.g_cin == 0 && g.B.g_cin == 0, "conv dW: layer %d is not a plain fp32 dW", k);
+        B2S_CHECK(g.M > 0 && g.N > 0 && g.M % 8 == 0 && g.N % 8 == 0 && g.A.ld % 8 == 0 && g.B.ld % 8 == 0 && g.A.ld >= g.M && g.B.ld >= g.N && g.ldc >= 5 * g.N,
+                  "conv dW: layer %d: cout = %d, cin = %d and the leading dimensions (%d, %d) must be multiples of 8, ldc = %d >= 5 cin", k, g.M, g.N,
+                  g.A.ld, g.B.ld, g.ldc);
+        B2S_CHECK(((uintptr_t)g.A.p % 16 == 0) && ((uintptr_t)g.B.p % 16 == 0), "conv dW: operands must be 16-byte aligned");
+        B2S_CHECK(!g.epi.bias && !g.epi.relu && !g.epi.relu_aux && !g.epi.residual && !g.epi.drop.thresh && !g.epi.row_len && !g.epi.colstat && !g.epi.kv_k,
+                  "conv dW: linear epilogue only");
+        g.A.R = g.B.R = g.K = B * T; g.A.C = g.M; g.B.C = g.N;
+        g.splitk = 1; g.ws = nullptr; g.ws_floats = 0; g.cs_o = g.cs_i = 0; g.A.bs_o = g.A.bs_i = g.B.bs_o = g.B.bs_i = 0;
+        g.epi.conv_dw_cin = g.N;
+        grp.p[k] = g;
+        grp.tile0[k] = tiles;
+        tiles += cdiv(g.M, t256::BM) * 5 * cdiv(g.N, 128);
+    }
+    grp.tile0[n] = tiles;
+    constexpr size_t smem = (size_t)t256::NSTAGE * t256::STAGE_BYTES;
+    static std::once_flag attr_once;
+    static hipError_t attr_err = hipSuccess;
+    std::call_once(attr_once, [] {
+        attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(t256::gemm_glds256_grouped_kernel<4, true>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    });
+    B2S_HIP(attr_err);
+    hipLaunchKernelGGL((t256::gemm_glds256_grouped_kernel<4, true>), dim3(tiles), dim3(t256::nthreads_of(false)), smem, stream, grp, zero);
     B2S_LAUNCH_CHECK();
     return 0;
 }

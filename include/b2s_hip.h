@@ -263,6 +263,9 @@ typedef struct b2s_gemm_desc {
     float drop_p;
     uint64_t seed;
     int32_t conv_cin_a, conv_T, conv_dw_cin; /* conv gather on A (token rows) */
+    /* conv_dw_cin > 0 with conv_T > 0 and conv_cin_a = 0 (bf16, trans_a = trans_b = 1, N = 5 cin): conv weight gradient straight from the token rows --
+     * A = dy [K = B * conv_T][M], B = the conv input [K][cin], C[co][ci*5 + j] (+)= sum over t of dy[b, t, co] * x[b, t + j - 2, ci] with the input
+     * zero outside [0, conv_len[b]) (conv_len = NULL: conv_T); cin, M, lda, ldb multiples of 8.  No gathered operand is built. */
     int32_t rows_per_batch;
 } b2s_gemm_desc;
 int b2s_gemm(const b2s_gemm_desc* d, const void* A, const void* B, void* C, const float* bias, const float* residual,
