@@ -38,6 +38,10 @@ _PROTOS = {
     "b2s_voc_silence_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "b2s_voc_silence_split": (C.c_int, [P, P, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, P, P, P, P, P, P, P, C.c_size_t, P]),
     "b2s_voc_silence_gather": (C.c_int, [P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P]),
+    # corpus preparation (b2s_hip/prep.py)
+    "b2s_voc_prep_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "b2s_voc_prep_trim": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, C.c_size_t, P]),
+    "b2s_voc_prep_abs_quantile": (C.c_int, [P, P, C.c_int, C.c_int, P, P, C.c_int, C.c_double, P, P, C.c_size_t, P]),
 }
 EXPORTS = sorted(_PROTOS)
 

@@ -1,5 +1,6 @@
-/* C ABI of libb2s_vocoder.so: batched Griffin-Lim vocoder (mel -> wav), mel front end (wav -> mel) and silence splitting / trimming
- * (the b2s_voc_silence_* calls at the end, which take their own parameters instead of B2SVocParams) for gfx950.
+/* C ABI of libb2s_vocoder.so: batched Griffin-Lim vocoder (mel -> wav), mel front end (wav -> mel), silence splitting / trimming
+ * (the b2s_voc_silence_* calls, which take their own parameters instead of B2SVocParams) and corpus preparation (the b2s_voc_prep_*
+ * calls at the end) for gfx950.  Eleven entry points.
  *
  * The reference's utils/audio.py (librosa 0.6.0 semantics) on the GPU, fp32 throughout.  Only n_fft 2048, win 800, hop 200 and
  * 80 mels are compiled in; any other value is refused with an error naming the supported set.  Utterances are packed ragged:
@@ -59,6 +60,44 @@ int b2s_voc_silence_split(const float *wav, const int32_t *lengths, int B, int L
  * zero from out_lengths[b] on.  A pure copy: kept samples are bit-equal to the input's. */
 int b2s_voc_silence_gather(const float *wav, int B, int Lmax, int frame_length, int hop_length, const int32_t *intervals,
                            const int32_t *n_intervals, const int32_t *prefix, const int32_t *out_lengths, float *wav_out, void *stream);
+
+/* Corpus preparation: the body of the reference's corpora/process_corpus.py trim_audios on a ragged batch (csrc/vocoder/prep.hip).
+ * wav [B, Lmax] fp32, lengths [B] int32 on the device, every L_b in 2..Lmax (a length outside is clamped, never read past).  Per utterance:
+ *   1. intervals = split at (top_db 40, frame_length 2048, hop 512); ref = max |y|, mv_i = max |y| over interval i
+ *   2. from the front, then from the back, while more than one interval is left: drop a zero-length interval; drop one with
+ *      (mv < ref / 10 or (len <= gap / 2 and mv < ref / 4)) and gap >= 4096, gap = the distance to its neighbour; stop at the first kept.
+ *      ref / 10 and ref / 4 are fp32 quotients of the fp32 maxima.  n_removed = intervals dropped.
+ *   3. status GAP if two neighbouring kept intervals are >= gap_threshold samples apart (the reference: 12288, or 16000 for some corpora)
+ *   4. v95 = the k-th smallest (0-based) |y| over the N samples of the kept intervals, k = (int)((double)N * 0.95): exactly
+ *      np.sort(np.abs(voiced))[int(len(voiced) * 0.95)], bit for bit, by a radix select on the bit patterns
+ *   5. scale = (float)(0.244 / (double)v95); y2 = y * scale in fp32, cropped to [first kept start, last kept end).  This is the
+ *      reference's arithmetic under the NumPy 1.x it was written for: a Python float divided by an fp32 scalar is fp64 there, and an
+ *      fp32 array times that scalar stays fp32 (NumPy 2 would do the division in fp32).
+ *   6. (l, r) = trim index of y2 at (40, 256, 64)
+ *   7. out = 1600 samples before l, y2[l:r], 2400 samples after r, taken from y2 where it has them and zero where not:
+ *      out_len = r - l + 4000.  status LENGTH unless 16000 <= out_len <= 320000.
+ * status SILENT: ref == 0 or v95 == 0.  The reference divides by zero there and writes a file of NaNs; skipping such a file under a
+ * name of its own is a deliberate deviation.  Precedence: GAP, then SILENT, then LENGTH.
+ *   out [B, Lmax + 4000] fp32, zero from out_lengths[b] on; out_lengths, status, n_removed [B] int32; v95 [B] fp32
+ * Of an utterance whose status is not OK only status and n_removed are specified; nothing is read or written out of bounds for it. */
+#define B2S_VOC_PREP_OK 0
+#define B2S_VOC_PREP_GAP 1
+#define B2S_VOC_PREP_LENGTH 2
+#define B2S_VOC_PREP_SILENT 3
+
+#define B2S_VOC_WS_PREP_TRIM 0
+#define B2S_VOC_WS_PREP_QUANTILE 1
+
+size_t b2s_voc_prep_ws_bytes(int B, int Lmax, int which);   /* 0 on an argument error (message set) */
+
+int b2s_voc_prep_trim(const float *wav, const int32_t *lengths, int B, int Lmax, int gap_threshold, float *out, int32_t *out_lengths,
+                      int32_t *status, int32_t *n_removed, float *v95, void *ws, size_t ws_bytes, void *stream);
+
+/* Step 4 alone.  intervals [B, NI, 2] int32: [start, end) sample ranges, ascending and disjoint (values outside 0..L_b are clamped),
+ * the first n_intervals[b] <= NI of every row used.  out[b] = the k-th smallest |y| over the N samples the intervals cover,
+ * k = min((int)((double)N * fraction), N - 1), 0 <= fraction < 1; 0.0f if N == 0.  Bit-equal to sorting, whatever the ties. */
+int b2s_voc_prep_abs_quantile(const float *wav, const int32_t *lengths, int B, int Lmax, const int32_t *intervals,
+                              const int32_t *n_intervals, int NI, double fraction, float *out, void *ws, size_t ws_bytes, void *stream);
 
 #ifdef __cplusplus
 }
