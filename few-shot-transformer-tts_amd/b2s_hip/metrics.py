@@ -31,6 +31,10 @@ _PROTOS = {
     "b2s_met_last_error": (C.c_char_p, []),
     "b2s_met_dtw_ws_bytes": (C.c_size_t, [_I, _I, _I, _I, _I, _I, _I, _I]),
     "b2s_met_dtw": (C.c_int, [P, P, _I, _I, P, P, _I, _I, _I, _I, _I, _I, P, P, P, P, P, P, P, C.c_size_t, P]),
+    # alignment-head selection (bound in b2s_hip.alignment)
+    "b2s_met_align_chunk": (C.c_int, []),
+    "b2s_met_align_ws_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
+    "b2s_met_align_select": (C.c_int, [P, _I, _I, _I, _I, _I, P, P, P, P, P, P, P, P, C.c_size_t, P]),
 }
 EXPORTS = sorted(_PROTOS)
 

@@ -20,6 +20,7 @@
 #include <cstdio>
 #include <string>
 #include "../../../include/b2s_metrics.h"
+#include "met_common.h"
 
 namespace {
 
@@ -31,17 +32,7 @@ constexpr int MAX_LEVELS = 40;
 constexpr int LDS_BYTES = 64 * 1024 - 1024;    // dynamic LDS per block (the static level table and scalars take the rest of 64 KiB)
 
 thread_local std::string g_err;
-
-int fail(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-int fail(const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return 1;
-}
+using b2s_met::fail;
 
 // LDS plan, sized by the longest sequences: distance tiles, the strip boundary row, per-row window / offsets, the coarse path's
 // row extents, then back-pointers in whatever is left.
@@ -388,6 +379,17 @@ __global__ __launch_bounds__(NT) void k_met_dtw(const float *__restrict__ x, con
 }
 
 }  // namespace
+
+// the library's one error slot (met_common.h): every source of libb2s_metrics.so reports through it
+int b2s_met::fail(const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return 1;
+}
 
 extern "C" {
 

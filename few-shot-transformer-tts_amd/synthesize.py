@@ -9,7 +9,9 @@ instead of once per frame (the reference syncs with torch.all every frame and re
 Results follow the reference: mel_pre / mel_aft [B, T_gen, M], generated_lengths including the reference's
 off-by-one for samples that never stop, exact zeros after a sample's stop, encoder-decoder alignments
 [B, H, S, T_gen] per layer.  Decoder self-attention alignments (which the reference returns but nothing reads)
-are produced only with keep_self_alignments=True.
+are produced only with keep_self_alignments=True.  With hp.align == "hip" the head that the reference's plot_attn would draw is
+picked on the device (b2s_hip.alignment) and alignments['encdec'] is ONE array [B, 1, S, T_gen] of the chosen maps, with the choice
+and its path diagnostics under alignments['selected'].
 """
 import copy
 import ctypes as C
@@ -62,9 +64,15 @@ def eval_batch(model_eval, data, use_bar=True, bar_interval=10, use_graph=True, 
     stays one lane (B2S_DECODE_LANES overrides); the option is for batches too large for one KV-cache allocation.
     device_results=True returns torch tensors on the device instead of NumPy arrays (no host copy).
     hp.mse_dtw == "hip" rebinds the reference's utils.infolog.calculate_mse_dtw to the GPU metric first (b2s_hip.metrics.install:
-    eval.py reaches this function after hp.parse and before every MSE-after-DTW call); the default "reference" leaves it alone."""
-    from b2s_hip import metrics
+    eval.py reaches this function after hp.parse and before every MSE-after-DTW call); the default "reference" leaves it alone.
+    hp.align == "hip": after the decode the head that plot_attn would choose is selected on the device for every utterance
+    (b2s_hip.alignment.select_alignments) and the per-layer alignments are freed: alignments['encdec'] is a list of one array
+    [B, 1, S, T_gen] (an unedited plot_attn over it draws the same picture), and alignments['selected'] holds `layer`, `head`,
+    `scores` [B, L, H], `focus` and `stats` [B, 4] (NumPy arrays, or tensors with device_results).  The host copy shrinks by
+    n_decoder_layer * n_attention_head."""
+    from b2s_hip import alignment, metrics
     metrics.install(hp)
+    align_hip = alignment.mode(hp) == "hip"
     with torch.no_grad():
         tic = time.time()
         batch = copy.copy(data)
@@ -189,6 +197,13 @@ def eval_batch(model_eval, data, use_bar=True, bar_interval=10, use_graph=True, 
         for ln in Ls:
             torch.cuda.current_stream().wait_stream(ln.stream)
         mel_aft = model_eval.postnet(mels, lengths, _fuse_add=True)        # mels + postnet(mels), BN in eval mode
+        sel_keys = ()
+        if align_hip:
+            sel = alignment.select_alignments(alignments['encdec'], batch['input_lengths'], lengths)
+            alignments['encdec'] = [sel['maps'].unsqueeze(1)]              # the per-layer tensors are freed here
+            sel_keys = ('layer', 'head', 'scores', 'focus', 'stats')
+            alignments['selected'] = {k: sel[k] for k in sel_keys}
+            del sel
         if device_results:
             # results stay in HBM as torch tensors (the reference returns NumPy arrays: synthesize.py:57-61 -- for 64 x 1000 frames
             # that is a 2 GB device-to-host copy of the alignments, which a caller that goes on working on the GPU skips)
@@ -196,9 +211,12 @@ def eval_batch(model_eval, data, use_bar=True, bar_interval=10, use_graph=True, 
             return {'names': data.get('names'), 'mel_pre': mels, 'mel_aft': mel_aft, 'alignments': alignments,
                     'input_lengths': batch['input_lengths'], 'generated_lengths': lengths}
         n_self = len(alignments['self'])
-        host = _to_host(alignments['self'] + alignments['encdec'] + [mels, mel_aft, lengths])
-        alignments = {'self': host[:n_self], 'encdec': host[n_self:-3]}
-        mel_pre_h, mel_aft_h, lengths_h = host[-3:]
+        n_sel = len(sel_keys)
+        host = _to_host(alignments['self'] + alignments['encdec'] + [mels, mel_aft, lengths] + [alignments['selected'][k] for k in sel_keys])
+        alignments = {'self': host[:n_self], 'encdec': host[n_self:len(host) - 3 - n_sel]}
+        mel_pre_h, mel_aft_h, lengths_h = host[len(host) - 3 - n_sel:len(host) - n_sel]
+        if n_sel:
+            alignments['selected'] = dict(zip(sel_keys, host[len(host) - n_sel:]))
         toc = time.time()
         total_length = int(lengths_h.sum())
         logging.info("Time: %.4f, Samples: %d, Length: %d, Max length: %d, Real-time Factor: %.4f" % (
@@ -245,7 +263,12 @@ def save_eval_results(names, mel_pre, mel_aft, alignments, input_lengths, genera
     is vocoded in one call before the pool starts and written with the package's save_wav.  `_trim.wav` needs the reference's
     trim_silence_intervals (librosa) with hp.trim == "reference"; with hp.trim == "hip" (which needs vocoder=hip) the vocoder's output
     stays on the device, the whole batch is trimmed there in one call (b2s_hip.vocoder.trim_silence_intervals_batch) and `_trim.wav`
-    is written from that.  If the vocoder fails as a whole, that is logged and the .npy files are still written."""
+    is written from that.  If the vocoder fails as a whole, that is logged and the .npy files are still written.
+
+    When `alignments` carries 'selected' (eval_batch with hp.align == "hip") the alignment figure needs no reference checkout:
+    `<name>_align.png` is drawn by b2s_hip.alignment.plot_selected (matplotlib only) from the one map per sample, titled with the
+    true layer and head, and `<name>_align.json` holds layer, head, score, focus and the four path statistics; both honour
+    n_plot_alignment.  A sample without a choice (layer -1) is logged as failed, as when the reference's plot_attn raises."""
     import threading
     import traceback
     from concurrent.futures import ThreadPoolExecutor
@@ -257,8 +280,15 @@ def save_eval_results(names, mel_pre, mel_aft, alignments, input_lengths, genera
         mel2wav = save_wav = trim_silence_intervals = None
     try:
         from utils.infolog import plot_attn, plot_mel
+        from utils.infolog import lock as plot_lock
     except Exception:                       # matplotlib / fastdtw are optional
-        plot_attn = plot_mel = None
+        plot_attn = plot_mel = plot_lock = None
+    selected = alignments.get('selected') if isinstance(alignments, dict) else None
+    if selected is not None:
+        import importlib.util
+        import json
+        from b2s_hip import alignment
+        can_plot = importlib.util.find_spec("matplotlib") is not None      # decided once; the diagnostics are written either way
     if hp.trim not in ("reference", "hip"):
         raise ValueError("unknown trim %r (expected 'reference' or 'hip')" % (hp.trim,))
     if hp.trim == "hip" and hp.vocoder == "reference":
@@ -298,9 +328,21 @@ def save_eval_results(names, mel_pre, mel_aft, alignments, input_lengths, genera
                     save_wav(trim_silence_intervals(wav), os.path.join(output_dir, '%s_trim.wav' % name))
             if plot_mel is not None:
                 plot_mel(os.path.join(output_dir, '%s_mel.png' % name), mel)
-                if n_plot_alignment is None or i < n_plot_alignment:
+                if selected is None and (n_plot_alignment is None or i < n_plot_alignment):
                     aligns = [np.asarray(a[i]).transpose([0, 2, 1]) for a in alignments["encdec"]]
                     plot_attn(aligns, os.path.join(output_dir, '%s_align.png' % name), enc_length=input_lengths[i], dec_length=n)
+            if selected is not None and (n_plot_alignment is None or i < n_plot_alignment):
+                info = alignment.summary(selected, i)
+                if info['layer'] < 0:
+                    raise ValueError("no alignment head of sample %s scores above 0 (%d frames)" % (name, n))
+                with open(os.path.join(output_dir, '%s_align.json' % name), 'w') as f:
+                    json.dump(info, f)
+                amap = np.asarray(alignments['encdec'][0][i][0]).T         # [dec, enc], cropped like plot_attn (a length 0 crops nothing)
+                enc_n = int(input_lengths[i])
+                amap = amap[:, :enc_n] if enc_n else amap
+                amap = amap[:n] if n else amap
+                if can_plot:                                               # under the lock plot_mel takes, where there is one
+                    alignment.plot_selected(amap, info, os.path.join(output_dir, '%s_align.png' % name), lock=plot_lock)
         except Exception:
             logging.error('Fail to produce eval output: ' + str(names[i]))
             logging.error(traceback.format_exc())

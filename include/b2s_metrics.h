@@ -1,5 +1,5 @@
 /* C ABI of libb2s_metrics.so: batched FastDTW (fastdtw 0.3.4 semantics, euclidean distance) and the MSE-after-DTW eval metric
- * for gfx950.
+ * for gfx950, and the selection of the alignment head that the eval plots (b2s_met_align_*, at the end).
  *
  * Utterances are packed ragged: frame f of pair b is row x_offsets[b] + f of x (x_offsets = exclusive prefix sum of the lengths,
  * B + 1 int32 entries on the device), fp32 rows of `dim` features, 1 <= dim <= 256; the same for y.  Distances, the pyramid and the
@@ -41,6 +41,29 @@ int b2s_met_dtw(const float *x, const int32_t *x_offsets, int total_x, int max_x
                 int total_y, int max_y, int B, int dim, int radius, int flags, double *cost_out, double *mse_out,
                 int32_t *path_len_out, int32_t *status_out, int32_t *path_out, const int32_t *path_offsets, void *ws,
                 size_t ws_bytes, void *stream);
+
+/* ---- alignment-head selection (csrc/metrics/align.hip) ----
+ * The reference's plot_attn picks, per utterance, the encoder-decoder attention head with the largest sum over decoder frames of the
+ * per-frame maximum over encoder positions, and draws that one map.  b2s_met_align_select does the selection on the device, so that
+ * one [S, T] map per utterance leaves it instead of n_layers * H, and summarises the chosen head's argmax path.
+ *
+ * layers: HOST array of n_layers (1..16) device pointers, each [B, H, S, T] contiguous fp32 with T innermost (what
+ * b2s_decode_alignment writes); they travel in the kernel arguments.  enc_len / dec_len: device int32 [B], clamped to [0, S] and
+ * [0, T]; rows s >= enc_len and frames t >= dec_len are never read.
+ *   scores_out[B, n_layers, H] f64 = sum_{t < dec_len} max_{s < enc_len} A_l[b, h, s, t]: the maximum exact in fp32, the sum fp64 in
+ *       a fixed order (per chunk of b2s_met_align_chunk() frames, then over the chunks), bit-reproducible from run to run
+ *   best_out[B] int32 = l * H + h of the largest score: strict > against a running best that starts at 0, layers then heads in order
+ *       (the first wins a tie); -1 when no score is > 0
+ *   map_out[B, S, T] f32 (nullable) = the chosen head's slab unchanged; zeros for best -1
+ *   path_out[B, T] int32 (nullable) = first index of the maximum over s < enc_len of the chosen head at frame t; -1 for t >= dec_len
+ *       and for best -1
+ *   stats_out[B, 4] int32 (nullable), over that path p: #{t >= 1: p[t] < p[t-1]}, max(p[t] - p[t-1], 0), the number of distinct
+ *       positions, p[dec_len - 1]; zeros when there is no path */
+int b2s_met_align_chunk(void);
+size_t b2s_met_align_ws_bytes(int B, int n_layers, int H, int S, int T);
+int b2s_met_align_select(const float *const *layers, int n_layers, int B, int H, int S, int T, const int32_t *enc_len,
+                         const int32_t *dec_len, double *scores_out, int32_t *best_out, float *map_out, int32_t *path_out,
+                         int32_t *stats_out, void *ws, size_t ws_bytes, void *stream);
 
 #ifdef __cplusplus
 }
