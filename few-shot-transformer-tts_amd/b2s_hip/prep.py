@@ -1,14 +1,19 @@
-"""Corpus preparation on the GPU: a directory of 16 kHz mono wavs -> proc_wavs/ -> mels/ -> mels.zip and its metadata.
+"""Corpus preparation on the GPU: a directory of wavs -> proc_wavs/ (16 kHz mono) -> mels/ -> mels.zip and its metadata.
 
 The reference's corpora/process_corpus.py (trim_audios, recollect_meta, build_mels, merge_datasets) with paths as arguments instead of
 its hard-coded ones, without librosa.  The body of trim_audios runs batched in libb2s_vocoder.so (b2s_voc_prep_trim, C ABI in
 include/b2s_vocoder.h; kernels in csrc/vocoder/prep.hip), the mels come from vocoder.wav2mel_batch.  There is no CPU fallback: CPU
 tensors are refused and a missing library is an error.
 
-    python -m b2s_hip.prep --corpus DIR=lang [--corpus DIR=lang ...] --packed DIR
+    python -m b2s_hip.prep --corpus DIR=lang [--corpus DIR=lang ...] --packed DIR [--resample hip]
 
-What is not built: resampling (a file that is not 16 kHz mono is refused), the per-dataset converters, statistics(), collect_samples()
-and the max95v plot.  One deliberate deviation: a file whose 95th-percentile amplitude (or peak) is zero is skipped as `silent`; the
+By default a file that is not 16 kHz mono is refused.  resample="hip" (--resample hip) switches on the first line of the reference's
+trim_audios, librosa.load(wav_file, sr=16000): np.mean over the channels and resampy's 'kaiser_best' interpolation, batched in
+libb2s_vocoder.so (b2s_voc_resample; kernels in csrc/vocoder/resample.hip).  The resampled batch stays on the device and goes straight
+into the trimming.  Parity is to a NumPy restatement of the published algorithm (tests/resample_ref.py); librosa and resampy themselves
+are not needed anywhere.
+
+What is not built: the per-dataset converters, statistics(), collect_samples() and the max95v plot; PCM24 and FLAC are not read.  One deliberate deviation: a file whose 95th-percentile amplitude (or peak) is zero is skipped as `silent`; the
 reference divides by zero there and writes NaNs.  proc_wavs are written as float32 wavs; the reference writes float64 where it padded
 with np.zeros and float32 elsewhere -- the sample values are the same.
 """
@@ -91,6 +96,74 @@ def trim_audios_batch(wavs, lengths, gap_threshold=12288):
     out, meta = _trim_device(wavs, lengths, gap_threshold)
     m = meta.cpu().numpy()
     return out, m[0].copy(), m[1].copy(), m[2].copy(), m[3].copy().view(np.float32)
+
+
+def _check_resample(resample):
+    if resample not in (None, "hip"):
+        raise ValueError("unknown resample %r (None or 'hip')" % (resample,))
+
+
+def resample_lengths(n, orig_sr):
+    """(n_valid, n_out) of n samples at orig_sr brought to 16 kHz: resampy interpolates int(n * ratio) samples and librosa's fix_length
+    pads with zeros to int(ceil(n * ratio)), both in Python floats with ratio = float(16000) / orig_sr."""
+    ratio = float(SR) / orig_sr
+    return int(n * ratio), int(np.ceil(n * ratio))
+
+
+def resample_tile(orig_sr):
+    """(outputs per workgroup, input samples staged per workgroup) of the resampling kernel for orig_sr: the rule of
+    csrc/vocoder/resample.hip (make_plan), restated for tests and benchmarks that want rows around those sizes."""
+    ratio = float(SR) / orig_sr
+    step = int(min(1.0, ratio) * 512)
+    tile = 4096
+    while True:
+        span = (int(np.ceil(tile * (1.0 / ratio))) + 2 * (32769 // step) + 4 + 3) // 4 * 4
+        if span <= 8064 or tile == 256:
+            return tile, span
+        tile //= 2
+
+
+def _resample_device(wavs, lengths, orig_sr):
+    """One b2s_voc_resample call, nothing synchronised: (out [B, Lmax_out] cuda fp32, n_out as a list)."""
+    lib = vocoder.load()
+    if isinstance(orig_sr, bool) or not isinstance(orig_sr, (int, np.integer)):
+        raise B2SError("orig_sr must be an integer number of Hz, got %r" % (orig_sr,))
+    if isinstance(wavs, np.ndarray):
+        wavs = torch.from_numpy(np.ascontiguousarray(wavs, dtype=np.float32)).cuda()
+    if wavs.dim() not in (2, 3):
+        raise B2SError("wavs must be [B, Lmax] or [B, Lmax, C], got %s" % (tuple(wavs.shape),))
+    if wavs.dtype != torch.float32:
+        raise B2SError("wavs must be float32, got %s" % wavs.dtype)
+    ptr(wavs)                                          # refuses CPU / non-contiguous tensors
+    B, Lmax = int(wavs.shape[0]), int(wavs.shape[1])
+    channels = int(wavs.shape[2]) if wavs.dim() == 3 else 1
+    samples = [int(n) for n in lengths]
+    if len(samples) != B:
+        raise B2SError("%d lengths for a batch of %d" % (len(samples), B))
+    if any(n < 1 or n > Lmax for n in samples):
+        raise B2SError("every length must be in 1..Lmax=%d samples (got %s)" % (Lmax, samples))
+    device = wavs.device
+    nbytes = lib.b2s_voc_resample_ws_bytes(B, Lmax, channels, int(orig_sr))
+    if nbytes == 0:
+        vocoder.check(1)
+    counts = np.array([resample_lengths(n, int(orig_sr)) for n in samples], dtype=np.int32).reshape(B, 2)
+    Lmax_out = max(1, int(counts[:, 1].max()))
+    meta = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.array(samples, np.int32)[:, None], counts], axis=1).T)).to(device)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    out = torch.empty(B, Lmax_out, dtype=torch.float32, device=device)
+    vocoder.check(lib.b2s_voc_resample(ptr(wavs), ptr(meta[0]), B, Lmax, channels, int(orig_sr), ptr(meta[1]), ptr(meta[2]), Lmax_out,
+                                       ptr(out), ptr(ws), ws.numel(), torch.cuda.current_stream(device).cuda_stream))
+    return out, [int(n) for n in counts[:, 1]]
+
+
+def resample_batch(wavs, lengths, orig_sr):
+    """librosa.load(..., sr=16000)'s arithmetic for every utterance of a padded batch (cuda tensor or NumPy, float32): [B, Lmax] mono or
+    [B, Lmax, C] interleaved with C in 1..8, per-utterance frame counts `lengths` (host sequence, every L_b in 1..Lmax; the padding may
+    hold anything), all at orig_sr Hz.  Channels are averaged like np.mean, then resampled with resampy's 'kaiser_best' filter; at
+    orig_sr == 16000 the result is the down-mix bit for bit.  Returns (out [B, Lmax_out] cuda fp32, zero from int(L_b * ratio) on,
+    out_lengths = int(ceil(L_b * ratio)) as an int32 NumPy array).  Runs on torch.cuda.current_stream() without synchronising."""
+    out, n_out = _resample_device(wavs, lengths, orig_sr)
+    return out, np.array(n_out, dtype=np.int32)
 
 
 def abs_quantile_batch(wavs, lengths, intervals, fraction=0.95):
@@ -184,11 +257,19 @@ def _refuse_unless_16k_mono(path, rate, channels):
                        "convert the file first" % (path, rate, channels, SR))
 
 
-def load_wav(path):
-    """librosa.load(path, sr=16000) for a file that already is 16 kHz mono; any other file is refused."""
+def load_wav(path, resample=None):
+    """librosa.load(path, sr=16000) for a file that already is 16 kHz mono; any other file is refused, unless resample="hip": then the
+    channels are averaged and the signal resampled to 16 kHz on the GPU (resample_batch)."""
+    _check_resample(resample)
     rate, channels, _ = wav_info(path)
-    _refuse_unless_16k_mono(path, rate, channels)
-    return read_wav(path)[0]
+    if resample is None or (rate == SR and channels == 1):
+        _refuse_unless_16k_mono(path, rate, channels)
+        return read_wav(path)[0]
+    y = read_wav(path)[0]
+    if y.shape[0] == 0:
+        return np.zeros(0, np.float32)
+    out, n_out = resample_batch(y[None], [y.shape[0]], rate)
+    return out[0, :n_out[0]].cpu().numpy()
 
 
 def write_wav_float32(path, y, sr=SR):
@@ -249,17 +330,44 @@ def _length_sorted_batches(items):
 
 
 def _padded(ws):
-    pad = np.zeros((len(ws), max(len(w) for w in ws)), np.float32)
+    pad = np.zeros((len(ws), max(len(w) for w in ws)) + ws[0].shape[1:], np.float32)
     for i, w in enumerate(ws):
         pad[i, :len(w)] = w
     return pad
 
 
-def trim_audios(corpus_dir, gap_threshold=None):
+def _write_trimmed(batch, trimmed, out_dir, res):
+    """The files of one trimmed batch (the result of trim_audios_batch for the paths in `batch`) and their counts."""
+    out, out_lens, status, n_removed, v95 = trimmed
+    out = out.cpu().numpy()
+    for i, path in enumerate(batch):
+        wav_name = os.path.basename(path)
+        if n_removed[i] > 1:
+            log.info("%s trimmed %d segments", wav_name, n_removed[i])
+        if status[i] == STATUS_GAP:
+            log.info("Skipped %s with gap", wav_name)
+            res["n_gap"] += 1
+        elif status[i] == STATUS_LENGTH:
+            log.info("Skipped %s with length %.2f", wav_name, out_lens[i] / float(SR))
+            res["n_len"] += 1
+        elif status[i] == STATUS_SILENT:
+            log.info("Skipped %s as silent", wav_name)
+            res["n_silent"] += 1
+        else:
+            write_wav_float32(os.path.join(out_dir, wav_name), out[i, :out_lens[i]])
+            res["max95v"].append(float(v95[i]))
+            continue
+        res["n_skip"] += 1
+
+
+def trim_audios(corpus_dir, gap_threshold=None, resample=None):
     """wavs/*.wav of one corpus -> proc_wavs/*.wav (float32): noise spikes at either end removed, files with a long inner gap skipped,
     the 95th-percentile amplitude of the voiced part scaled to 0.244, 1600 / 2400 samples of margin, files outside 1..20 s skipped.
     gap_threshold=None applies the reference's rule by corpus name.  A corpus whose proc_wavs/ exists is left alone (returns None).
+    A file that is not 16 kHz mono is refused, unless resample="hip": then such files are batched by (rate, channels) and by the length
+    they will have at 16 kHz, down-mixed and resampled on the device (resample_batch) and trimmed from there.
     Returns {"n_files", "n_skip", "n_gap", "n_len", "n_silent", "max95v": [v95 of every file written]}."""
+    _check_resample(resample)
     name = _corpus_name(corpus_dir)
     out_dir = os.path.join(corpus_dir, "proc_wavs")
     if os.path.exists(out_dir):
@@ -269,10 +377,17 @@ def trim_audios(corpus_dir, gap_threshold=None):
     files = sorted(glob.glob(os.path.join(corpus_dir, "wavs", "*.wav")))
     log.info("%s %d files", name, len(files))
     res = {"n_files": len(files), "n_skip": 0, "n_gap": 0, "n_len": 0, "n_silent": 0, "max95v": []}
-    items = []
+    items, foreign = [], defaultdict(list)
     for path in files:
         rate, channels, frames = wav_info(path)
-        _refuse_unless_16k_mono(path, rate, channels)
+        if resample is None or (rate == SR and channels == 1):
+            _refuse_unless_16k_mono(path, rate, channels)
+        else:
+            n_out = resample_lengths(frames, rate)[1]
+            if n_out >= 2:
+                foreign[(rate, channels)].append((n_out, path))
+                continue
+            frames = n_out
         if frames < 2:
             log.info("Skipped %s with length %.2f", os.path.basename(path), frames / float(SR))
             res["n_len"] += 1
@@ -282,26 +397,12 @@ def trim_audios(corpus_dir, gap_threshold=None):
     os.makedirs(out_dir)
     for batch in _length_sorted_batches(items):
         ws = [read_wav(p)[0] for p in batch]
-        out, out_lens, status, n_removed, v95 = trim_audios_batch(_padded(ws), [len(w) for w in ws], thres)
-        out = out.cpu().numpy()
-        for i, path in enumerate(batch):
-            wav_name = os.path.basename(path)
-            if n_removed[i] > 1:
-                log.info("%s trimmed %d segments", wav_name, n_removed[i])
-            if status[i] == STATUS_GAP:
-                log.info("Skipped %s with gap", wav_name)
-                res["n_gap"] += 1
-            elif status[i] == STATUS_LENGTH:
-                log.info("Skipped %s with length %.2f", wav_name, out_lens[i] / float(SR))
-                res["n_len"] += 1
-            elif status[i] == STATUS_SILENT:
-                log.info("Skipped %s as silent", wav_name)
-                res["n_silent"] += 1
-            else:
-                write_wav_float32(os.path.join(out_dir, wav_name), out[i, :out_lens[i]])
-                res["max95v"].append(float(v95[i]))
-                continue
-            res["n_skip"] += 1
+        _write_trimmed(batch, trim_audios_batch(_padded(ws), [len(w) for w in ws], thres), out_dir, res)
+    for (rate, channels), group in sorted(foreign.items()):
+        for batch in _length_sorted_batches(group):              # the batch rule applies to the lengths at 16 kHz
+            ws = [read_wav(p)[0] for p in batch]
+            dev, n_out = _resample_device(_padded(ws), [len(w) for w in ws], rate)
+            _write_trimmed(batch, trim_audios_batch(dev, n_out, thres), out_dir, res)
     log.info("Total skipped %d files (%d for gap, %d for length, %d silent)", res["n_skip"], res["n_gap"], res["n_len"], res["n_silent"])
     return res
 
@@ -419,6 +520,8 @@ def main(argv=None):
     ap.add_argument("--gap-threshold", type=int, default=None, help="samples; default: the reference's rule by corpus name")
     ap.add_argument("--min-speaker-samples", type=int, default=None)
     ap.add_argument("--n-eval", type=int, default=100)
+    ap.add_argument("--resample", choices=["hip"], default=None,
+                    help="hip: down-mix and resample files that are not 16 kHz mono on the GPU; default: refuse them")
     a = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     dirs, langs = [], []
@@ -431,7 +534,7 @@ def main(argv=None):
     import hyperparams
     hyperparams.hparams.override_from_dict(hyperparams.DEFAULTS)
     for d in dirs:
-        trim_audios(d, a.gap_threshold)
+        trim_audios(d, a.gap_threshold, a.resample)
         recollect_meta(d, a.min_speaker_samples)
         build_mels(d)
     print(json.dumps(merge_datasets(dirs, langs, a.packed, a.n_eval)))

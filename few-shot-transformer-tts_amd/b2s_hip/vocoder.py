@@ -1,5 +1,5 @@
-"""ctypes binding of libb2s_vocoder.so (C ABI in include/b2s_vocoder.h): batched Griffin-Lim vocoder, mel front end and silence
-splitting / trimming on the GPU.
+"""ctypes binding of libb2s_vocoder.so (C ABI in include/b2s_vocoder.h): batched Griffin-Lim vocoder, mel front end, silence
+splitting / trimming, corpus preparation and resampling to 16 kHz on the GPU.
 
 The reference's utils/audio.py surface (mel2wav, get_spectrograms, save_wav, trim_silence_intervals) and librosa.effects.split / trim
 with librosa 0.6.0 semantics, run as HIP kernels for gfx950.  There is no CPU fallback: CPU tensors are refused and a missing library
@@ -42,6 +42,9 @@ _PROTOS = {
     "b2s_voc_prep_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "b2s_voc_prep_trim": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, C.c_size_t, P]),
     "b2s_voc_prep_abs_quantile": (C.c_int, [P, P, C.c_int, C.c_int, P, P, C.c_int, C.c_double, P, P, C.c_size_t, P]),
+    # down-mix and resampling to 16 kHz (b2s_hip/prep.py)
+    "b2s_voc_resample_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "b2s_voc_resample": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, C.c_int, P, P, C.c_size_t, P]),
 }
 EXPORTS = sorted(_PROTOS)
 

@@ -27,8 +27,8 @@ echo "built $OUT"
 # the vocoder / mel front end is a library of its own (include/b2s_vocoder.h); not part of the measurement build
 if [ "$1" != "--lab" ]; then
   VOUT=../libb2s_vocoder.so
-  if [ "$1" = "--clean" ] || [ ! -f $VOUT ] || [ vocoder/vocoder.hip -nt $VOUT ] || [ vocoder/silence.hip -nt $VOUT ] || [ vocoder/prep.hip -nt $VOUT ] || [ ../../include/b2s_vocoder.h -nt $VOUT ]; then
-    hipcc $FLAGS -shared vocoder/vocoder.hip vocoder/silence.hip vocoder/prep.hip -o $VOUT
+  if [ "$1" = "--clean" ] || [ ! -f $VOUT ] || [ vocoder/vocoder.hip -nt $VOUT ] || [ vocoder/silence.hip -nt $VOUT ] || [ vocoder/prep.hip -nt $VOUT ] || [ vocoder/resample.hip -nt $VOUT ] || [ ../../include/b2s_vocoder.h -nt $VOUT ]; then
+    hipcc $FLAGS -shared vocoder/vocoder.hip vocoder/silence.hip vocoder/prep.hip vocoder/resample.hip -o $VOUT
   fi
   echo "built $VOUT"
   # batched FastDTW / MSE-after-DTW eval metric and alignment-head selection: a library of its own too (include/b2s_metrics.h)

@@ -1,6 +1,6 @@
 /* C ABI of libb2s_vocoder.so: batched Griffin-Lim vocoder (mel -> wav), mel front end (wav -> mel), silence splitting / trimming
- * (the b2s_voc_silence_* calls, which take their own parameters instead of B2SVocParams) and corpus preparation (the b2s_voc_prep_*
- * calls at the end) for gfx950.  Eleven entry points.
+ * (the b2s_voc_silence_* calls, which take their own parameters instead of B2SVocParams), corpus preparation (the b2s_voc_prep_*
+ * calls) and down-mixing / resampling to 16 kHz (the b2s_voc_resample* calls at the end) for gfx950.  Thirteen entry points.
  *
  * The reference's utils/audio.py (librosa 0.6.0 semantics) on the GPU, fp32 throughout.  Only n_fft 2048, win 800, hop 200 and
  * 80 mels are compiled in; any other value is refused with an error naming the supported set.  Utterances are packed ragged:
@@ -98,6 +98,28 @@ int b2s_voc_prep_trim(const float *wav, const int32_t *lengths, int B, int Lmax,
  * k = min((int)((double)N * fraction), N - 1), 0 <= fraction < 1; 0.0f if N == 0.  Bit-equal to sorting, whatever the ties. */
 int b2s_voc_prep_abs_quantile(const float *wav, const int32_t *lengths, int B, int Lmax, const int32_t *intervals,
                               const int32_t *n_intervals, int NI, double fraction, float *out, void *ws, size_t ws_bytes, void *stream);
+
+/* Down-mix and resampling to 16 kHz: the arithmetic of librosa 0.6.0's load(path, sr=16000) on a ragged batch (csrc/vocoder/resample.hip).
+ * wav [B, Lmax_in, channels] fp32 (interleaved, padded), lengths [B] int32 frames on the device (clamped into 0..Lmax_in; the padding past
+ * a length may hold anything and is never read).  One sample rate and one channel count per call.  Per utterance:
+ *   1. mono = np.mean over the channels: a left-to-right fp32 sum, one fp32 division by `channels` (1..8; 1 is used as it is)
+ *   2. orig_sr == 16000: out = mono, bit for bit.  Otherwise resampy's 'kaiser_best' filter: 64 zero crossings, 512 table steps per
+ *      crossing, rolloff 0.9475937167399596, Kaiser beta 14.769656459379492, the table scaled by ratio = 16000 / orig_sr when that
+ *      is < 1, index_step = (int)(min(1, ratio) * 512).  For t < n_valid[b]: time = t * (1 / ratio), n = (int)time,
+ *      frac = min(1, ratio) * (time - n) in fp64; out[t] = sum over the left wing (x[n - i]) then the right wing (x[n + 1 + k]) of
+ *      (win[o] + eta * (win[o + 1] - win[o])) * x, o = off + i * index_step, off = (int)(frac * 512), eta = frac * 512 - off,
+ *      the right wing with frac' = min(1, ratio) - frac.  The table is fp32 (computed in fp64), the sum is fp32.
+ *   3. out [B, Lmax_out] fp32 is zero from n_valid[b] to Lmax_out (librosa's fix_length to n_out[b] pads with zeros).
+ * n_valid [B] = int(N * ratio) and n_out [B] = int(ceil(N * ratio)), int32 on the device, are the caller's: computed in Python floats
+ * exactly as written and never recomputed here (n_out only documents the row's length; nothing past n_valid is non-zero).
+ * The filter table is rebuilt into the workspace on every call (32 770 entries); nothing is kept between calls.  A workgroup
+ * interpolates a tile of 4096 consecutive outputs of one utterance, halved (down to 256) until the input span of the tile,
+ * ceil(tile / ratio) + 2 * (32769 / index_step) + 4 samples rounded up to a multiple of 4, is at most 8064 floats: it is staged
+ * in LDS beside the table.  b2s_hip.prep.resample_tile(orig_sr) restates that rule.  orig_sr in 4000..192000. */
+size_t b2s_voc_resample_ws_bytes(int B, int Lmax_in, int channels, int orig_sr);   /* 0 on an argument error (message set) */
+
+int b2s_voc_resample(const float *wav, const int32_t *lengths, int B, int Lmax_in, int channels, int orig_sr, const int32_t *n_valid,
+                     const int32_t *n_out, int Lmax_out, float *out, void *ws, size_t ws_bytes, void *stream);
 
 #ifdef __cplusplus
 }
