@@ -35,6 +35,9 @@ _PROTOS = {
     "b2s_met_align_chunk": (C.c_int, []),
     "b2s_met_align_ws_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
     "b2s_met_align_select": (C.c_int, [P, _I, _I, _I, _I, _I, P, P, P, P, P, P, P, P, C.c_size_t, P]),
+    # batched edit distance behind the CER (bound in b2s_hip.cer)
+    "b2s_met_edit_max_len": (C.c_int, []),
+    "b2s_met_edit_distance": (C.c_int, [P, P, _I, _I, P, P, _I, _I, _I, P, P, P, P]),
 }
 EXPORTS = sorted(_PROTOS)
 

@@ -31,10 +31,10 @@ if [ "$1" != "--lab" ]; then
     hipcc $FLAGS -shared vocoder/vocoder.hip vocoder/silence.hip vocoder/prep.hip vocoder/resample.hip -o $VOUT
   fi
   echo "built $VOUT"
-  # batched FastDTW / MSE-after-DTW eval metric and alignment-head selection: a library of its own too (include/b2s_metrics.h)
+  # batched FastDTW / MSE-after-DTW eval metric, alignment-head selection and edit distance: a library of its own too (include/b2s_metrics.h)
   MOUT=../libb2s_metrics.so
-  if [ "$1" = "--clean" ] || [ ! -f $MOUT ] || [ metrics/dtw.hip -nt $MOUT ] || [ metrics/align.hip -nt $MOUT ] || [ metrics/met_common.h -nt $MOUT ] || [ ../../include/b2s_metrics.h -nt $MOUT ]; then
-    hipcc $FLAGS -shared metrics/dtw.hip metrics/align.hip -o $MOUT
+  if [ "$1" = "--clean" ] || [ ! -f $MOUT ] || [ metrics/dtw.hip -nt $MOUT ] || [ metrics/align.hip -nt $MOUT ] || [ metrics/edit.hip -nt $MOUT ] || [ metrics/met_common.h -nt $MOUT ] || [ ../../include/b2s_metrics.h -nt $MOUT ]; then
+    hipcc $FLAGS -shared metrics/dtw.hip metrics/align.hip metrics/edit.hip -o $MOUT
   fi
   echo "built $MOUT"
 fi

@@ -15,7 +15,9 @@ utils.audio.trim_silence_intervals, i.e. librosa, when importable) or "hip" (the
 vocoder=hip, whose waveforms it trims on the device); and `align`: "reference" (default: eval_batch returns every encoder-decoder
 alignment, n_decoder_layer arrays of [B, H, S, T_gen], and the reference's plot_attn picks one per sample on the host) or "hip"
 (b2s_hip.alignment picks it on the device: one map per sample comes back, with the chosen layer / head and path diagnostics, and
-save_eval_results writes `_align.png` / `_align.json` from those).
+save_eval_results writes `_align.png` / `_align.json` from those); and `cer`: "reference" (default: the reference's
+utils.transcribe scores with the editdistance package) or "hip" (eval_batch rebinds that module's `editdistance` to the batched GPU
+edit distance of b2s_hip.cer).
 """
 from utils.hparams import HParams
 
@@ -61,7 +63,7 @@ _SIGNAL = dict(
 
 # MI355X build additions (not in the reference)
 _BUILD = dict(compute_dtype="fp32", guided_attention_weight=0.0, guided_attention_sigma=0.2, freeze_encoder=False,
-              vocoder="reference", mse_dtw="reference", trim="reference", align="reference")
+              vocoder="reference", mse_dtw="reference", trim="reference", align="reference", cer="reference")
 
 _GROUPS = (_MODEL, _OPTIMISER, _BATCHING, _EVAL, _SIGNAL, _BUILD)
 assert sum(len(g) for g in _GROUPS) == len(set().union(*_GROUPS)), "a hyper-parameter is defined in two groups"

@@ -65,13 +65,16 @@ def eval_batch(model_eval, data, use_bar=True, bar_interval=10, use_graph=True, 
     device_results=True returns torch tensors on the device instead of NumPy arrays (no host copy).
     hp.mse_dtw == "hip" rebinds the reference's utils.infolog.calculate_mse_dtw to the GPU metric first (b2s_hip.metrics.install:
     eval.py reaches this function after hp.parse and before every MSE-after-DTW call); the default "reference" leaves it alone.
+    hp.cer == "hip" likewise rebinds the `editdistance` that the reference's utils.transcribe scores with to the GPU edit distance
+    (b2s_hip.cer.install), before run_transcription runs.
     hp.align == "hip": after the decode the head that plot_attn would choose is selected on the device for every utterance
     (b2s_hip.alignment.select_alignments) and the per-layer alignments are freed: alignments['encdec'] is a list of one array
     [B, 1, S, T_gen] (an unedited plot_attn over it draws the same picture), and alignments['selected'] holds `layer`, `head`,
     `scores` [B, L, H], `focus` and `stats` [B, 4] (NumPy arrays, or tensors with device_results).  The host copy shrinks by
     n_decoder_layer * n_attention_head."""
-    from b2s_hip import alignment, metrics
+    from b2s_hip import alignment, cer, metrics
     metrics.install(hp)
+    cer.install(hp)
     align_hip = alignment.mode(hp) == "hip"
     with torch.no_grad():
         tic = time.time()

@@ -1,5 +1,6 @@
 /* C ABI of libb2s_metrics.so: batched FastDTW (fastdtw 0.3.4 semantics, euclidean distance) and the MSE-after-DTW eval metric
- * for gfx950, and the selection of the alignment head that the eval plots (b2s_met_align_*, at the end).
+ * for gfx950, the selection of the alignment head that the eval plots (b2s_met_align_*) and the batched edit distance behind the
+ * eval's CER (b2s_met_edit_*, at the end).
  *
  * Utterances are packed ragged: frame f of pair b is row x_offsets[b] + f of x (x_offsets = exclusive prefix sum of the lengths,
  * B + 1 int32 entries on the device), fp32 rows of `dim` features, 1 <= dim <= 256; the same for y.  Distances, the pyramid and the
@@ -64,6 +65,24 @@ size_t b2s_met_align_ws_bytes(int B, int n_layers, int H, int S, int T);
 int b2s_met_align_select(const float *const *layers, int n_layers, int B, int H, int S, int T, const int32_t *enc_len,
                          const int32_t *dec_len, double *scores_out, int32_t *best_out, float *map_out, int32_t *path_out,
                          int32_t *stats_out, void *ws, size_t ws_bytes, void *stream);
+
+/* ---- batched edit distance (csrc/metrics/edit.hip) ----
+ * Levenshtein distance with unit costs over ragged pairs of int32 symbol sequences (code points, bytes, word ids: only equality is
+ * used): symbol i of side a of pair p is a[a_offsets[p] + i], offsets as above (exclusive prefix sums, B + 1 int32 on the device).
+ * a is the truth, b the prediction; each side holds at most b2s_met_edit_max_len() = 4096 symbols, and max_a / max_b (0..4096) bound
+ * every pair's lengths (the launch is sized by max_b).  Per pair the result is the lexicographically smallest (cost, substitutions)
+ * over all alignments, which fixes the breakdown: del - ins = len_a - len_b and cost = sub + del + ins.  A deletion is a truth symbol
+ * missing from the prediction, an insertion the reverse.  An empty side is no error: cost = the other side's length.
+ *   dist_out[B] int32 = cost; -1 where status is FAILED
+ *   ops_out[B, 3] int32 (nullable) = sub, del, ins; -1, -1, -1 where status is FAILED
+ *   status_out[B] int32 = B2S_MET_OK, or B2S_MET_FAILED for a pair whose offsets decrease or run outside 0..total_*, or whose length
+ *       exceeds max_*: its symbols are not read
+ * One launch on the caller's stream, no workspace; B <= 0, negative totals, max_* outside 0..4096 and NULL required pointers are
+ * refused on the host. */
+int b2s_met_edit_max_len(void);
+int b2s_met_edit_distance(const int32_t *a, const int32_t *a_offsets, int total_a, int max_a, const int32_t *b,
+                          const int32_t *b_offsets, int total_b, int max_b, int B, int32_t *dist_out, int32_t *ops_out,
+                          int32_t *status_out, void *stream);
 
 #ifdef __cplusplus
 }
