@@ -1942,6 +1942,8 @@ extern "C" int b2s_postnet_forward(b2s_model* m, const float* inputs, const int3
     B2S_TRY(check_bound(m));
     const b2s_config& cf = m->cfg;
     B2S_CHECK(inputs && lengths && out && ws && B > 0 && T > 0, "bad argument");
+    // (BatchNorm1d of the reference raises here too: one value has no variance, and its unbiased estimate M / (M - 1) is 0 * inf)
+    B2S_CHECK(!train || (long)B * T > 1, "Expected more than 1 value per channel when training, got B=%d T=%d (BatchNorm batch statistics)", B, T);
     hipStream_t st = S_(stream);
     b2s_ctx* c = new b2s_ctx();
     c->kind = 3; c->B = B; c->T = T; c->train = train; c->seed = seed; c->tgt_len = lengths;
@@ -1955,8 +1957,8 @@ extern "C" int b2s_postnet_forward(b2s_model* m, const float* inputs, const int3
     const float pd = train ? cf.decoder_dropout_rate : 0.f;
     // Training: the batch statistics are column sums taken by the conv GEMM's epilogue (GemmEpilogue::colstat) and turned into mean /
     // rstd / running statistics by the normalisation kernel itself: conv + one row kernel per layer (was conv + memset + two reduction
-    // passes + finalize + apply).  Evaluation (running statistics) and a one-row batch (a statistics pass of its own) take the statistics first.
-    const bool fused_stats = train && M > 1;
+    // passes + finalize + apply).  Evaluation takes the running statistics first.
+    const bool fused_stats = train != 0;
     auto run = [&]() -> int {
         B2S_TRY(ro_cast(dt, inputs, c->u[0], M * cf.num_mels, st));
         if (fused_stats) B2S_HIP(hipMemsetAsync(ps.stat, 0, sizeof(float) * (size_t)n * ps.stat_stride, st));
@@ -1978,11 +1980,7 @@ extern "C" int b2s_postnet_forward(b2s_model* m, const float* inputs, const int3
                                           last ? nullptr : c->u[i + 1], last ? out : nullptr, last ? add : nullptr, (int)M, cout, d, st));
                 continue;
             }
-            if (train)
-                B2S_TRY(ro_bn_stats(c->y[i], (int)M, cout, c->bn_mean[i], c->bn_rstd[i], 1e-5f, m->P(q + "running_mean"),
-                                    m->P(q + "running_var"), (long*)m->data[m->id(q + "num_batches_tracked")], 0.1f, sums, st));
-            else
-                B2S_TRY(ro_bn_eval_stats(m->P(q + "running_mean"), m->P(q + "running_var"), c->bn_mean[i], c->bn_rstd[i], 1e-5f, cout, st));
+            B2S_TRY(ro_bn_eval_stats(m->P(q + "running_mean"), m->P(q + "running_var"), c->bn_mean[i], c->bn_rstd[i], 1e-5f, cout, st));
             if (!last)
                 B2S_TRY(ro_bn_apply(dt, c->y[i], c->bn_mean[i], c->bn_rstd[i], m->P(q + "weight"), m->P(q + "bias"), 1, c->u[i + 1],
                                     nullptr, nullptr, (int)M, cout, d, st));

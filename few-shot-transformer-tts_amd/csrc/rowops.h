@@ -81,8 +81,6 @@ int ro_colsum(int dtype, const void* X, int x_fp32, int ldx, const float* wgt, f
               int C, hipStream_t st);
 
 // BatchNorm1d over all M = B*T rows (tacotron.py:83-89)
-int ro_bn_stats(const float* y, int M, int C, float* mean, float* rstd, float eps, float* running_mean,
-                float* running_var, long* num_batches_tracked, float momentum, float* scratch, hipStream_t st);
 int ro_bn_apply_train(int dtype, const float* y, const float* sums, float* mean, float* rstd, float eps, float* running_mean, float* running_var,
                       long* num_batches_tracked, float momentum, const float* gamma, const float* beta, int use_tanh, void* outT, float* out32,
                       const float* add32, int M, int C, DropCfg drop, hipStream_t st);

@@ -669,37 +669,6 @@ __global__ __launch_bounds__(256) void k_colsum(const T* X, int ldx, const float
 }
 
 // ---------------------------------------------------------------------------------- BatchNorm
-__global__ __launch_bounds__(256) void k_bn_colred(const float* y, int M, int C, const float* mu_sum, float* out) {
-    // mu_sum == nullptr: out[c] += sum_m y ; else out[c] += sum_m (y - mu_sum[c]/M)^2
-    __shared__ float sh[4][64];
-    const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + cx;
-    float acc = 0.f;
-    if (c < C) {
-        const float mu = mu_sum ? mu_sum[c] / M : 0.f;
-        for (int m = blockIdx.y * 4 + ry; m < M; m += gridDim.y * 4) {
-            float v = y[(long)m * C + c];
-            if (mu_sum) { v -= mu; v *= v; }
-            acc += v;
-        }
-    }
-    sh[ry][cx] = acc;
-    __syncthreads();
-    if (ry == 0 && c < C) atomicAdd(out + c, sh[0][cx] + sh[1][cx] + sh[2][cx] + sh[3][cx]);
-}
-__global__ void k_bn_finalize(const float* scratch, int M, int C, float* mean, float* rstd, float eps, float* rm,
-                              float* rv, long* nbt, float mom) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < C) {
-        float mu = scratch[c] / M, var = scratch[C + c] / M;
-        mean[c] = mu; rstd[c] = 1.f / sqrtf(var + eps);
-        if (rm) {
-            rm[c] = (1.f - mom) * rm[c] + mom * mu;
-            rv[c] = (1.f - mom) * rv[c] + mom * var * ((float)M / (float)(M - 1));
-        }
-    }
-    if (c == 0 && nbt) *nbt += 1;
-}
 __global__ void k_bn_eval_stats(const float* rm, const float* rv, float* mean, float* rstd, float eps, int C) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c < C) { mean[c] = rm[c]; rstd[c] = 1.f / sqrtf(rv[c] + eps); }
@@ -754,6 +723,10 @@ __global__ void k_bn_bwd_apply(const TD* dout, const float* y, const float* mean
 // the first use (one memory round trip per thread), 4 row lanes per workgroup.  The scalar kernels above read 4 bytes per lane and
 // walked their rows one dependent round trip at a time (1-2 TB/s).
 constexpr int BN_RU = 8;
+// The batch variance is one-pass, sum(y^2) / M - mean^2, from the conv GEMM's column sums: fine while a channel's |mean| / std stays below ~8.  A
+// handful of rows can put any ratio on a channel (two rows: whatever the two values are), so up to this many rows the variance is taken again as
+// sum((y - mean)^2) / M from y itself, which costs nothing at that size.
+constexpr int BN_TWO_PASS_M = 64;
 __device__ __forceinline__ float fast_tanh(float x) { return 1.f - 2.f / (__expf(2.f * x) + 1.f); }      // (|err| ~ 1e-7: exp overflow -> 1, underflow -> -1)
 struct BnStat {                   // how the forward kernel gets mean / rstd
     const float* sums;            // train: [2C] column sums of y and y^2 (written by the conv GEMM's epilogue); null: mean / rstd given
@@ -762,7 +735,7 @@ struct BnStat {                   // how the forward kernel gets mean / rstd
     float eps, mom;
 };
 // out = dropout(tanh?(gamma * (y - mean) * rstd + beta)) [+ add32]; in training mode mean / rstd come from the column sums and the
-// workgroups of grid row 0 also store them and update the running statistics (k_bn_finalize's job, without its launch)
+// workgroups of grid row 0 also store them and update the running statistics
 template <typename T>
 __global__ __launch_bounds__(256) void k_bn_apply_v(const float* __restrict__ y, BnStat bs, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                     int use_tanh, T* __restrict__ outT, float* __restrict__ out32, const float* __restrict__ add32, int M,
@@ -775,8 +748,17 @@ __global__ __launch_bounds__(256) void k_bn_apply_v(const float* __restrict__ y,
         const float4 s1 = ld4(bs.sums + c), s2 = ld4(bs.sums + C + c);
         const float im = 1.f / M;
         mu = make_float4(s1.x * im, s1.y * im, s1.z * im, s1.w * im);
-        const float4 var = make_float4(fmaxf(s2.x * im - mu.x * mu.x, 0.f), fmaxf(s2.y * im - mu.y * mu.y, 0.f), fmaxf(s2.z * im - mu.z * mu.z, 0.f),
-                                       fmaxf(s2.w * im - mu.w * mu.w, 0.f));
+        float4 var = make_float4(fmaxf(s2.x * im - mu.x * mu.x, 0.f), fmaxf(s2.y * im - mu.y * mu.y, 0.f), fmaxf(s2.z * im - mu.z * mu.z, 0.f),
+                                 fmaxf(s2.w * im - mu.w * mu.w, 0.f));
+        if (M <= BN_TWO_PASS_M) {                        // (every thread of every workgroup: the same rows in the same order, so the same value)
+            float4 q = make_float4(0, 0, 0, 0);
+            for (int m = 0; m < M; ++m) {
+                const float4 t = ld4(y + (long)m * C + c);
+                const float dx = t.x - mu.x, dy = t.y - mu.y, dz = t.z - mu.z, dw = t.w - mu.w;
+                q.x += dx * dx; q.y += dy * dy; q.z += dz * dz; q.w += dw * dw;
+            }
+            var = make_float4(q.x * im, q.y * im, q.z * im, q.w * im);
+        }
         rs = make_float4(1.f / sqrtf(var.x + bs.eps), 1.f / sqrtf(var.y + bs.eps), 1.f / sqrtf(var.z + bs.eps), 1.f / sqrtf(var.w + bs.eps));
         if (blockIdx.y == 0 && ry == 0 && own) {
             st4(bs.mean + c, mu); st4(bs.rstd + c, rs);
@@ -1412,17 +1394,6 @@ int ro_colsum(int dtype, const void* X, int x_fp32, int ldx, const float* wgt, f
         hipLaunchKernelGGL((k_colsum<float>), grid, dim3(256), 0, st, (const float*)X, ldx, wgt, out, M, C);
     else
         hipLaunchKernelGGL((k_colsum<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)X, ldx, wgt, out, M, C);
-    B2S_LAUNCH_CHECK(); return 0;
-}
-int ro_bn_stats(const float* y, int M, int C, float* mean, float* rstd, float eps, float* running_mean,
-                float* running_var, long* num_batches_tracked, float momentum, float* scratch, hipStream_t st) {
-    B2S_HIP(hipMemsetAsync(scratch, 0, sizeof(float) * 2 * C, st));
-    int gy = cdiv(M, 4 * 16); if (gy > 128) gy = 128; if (gy < 1) gy = 1;
-    dim3 grid(cdiv(C, 64), gy);
-    hipLaunchKernelGGL(k_bn_colred, grid, dim3(256), 0, st, y, M, C, (const float*)nullptr, scratch);
-    hipLaunchKernelGGL(k_bn_colred, grid, dim3(256), 0, st, y, M, C, (const float*)scratch, scratch + C);
-    hipLaunchKernelGGL(k_bn_finalize, dim3(cdiv(C, 256)), dim3(256), 0, st, (const float*)scratch, M, C, mean, rstd, eps,
-                       running_mean, running_var, num_batches_tracked, momentum);
     B2S_LAUNCH_CHECK(); return 0;
 }
 int ro_bn_eval_stats(const float* running_mean, const float* running_var, float* mean, float* rstd, float eps, int C,
