@@ -859,39 +859,9 @@ __global__ __launch_bounds__(256) void k_bn_bwd_v(const TD* __restrict__ dout, c
 
 // ---------------------------------------------------------------------------------- loss
 __device__ inline float softplusf(float x) { return fmaxf(x, 0.f) + log1pf(__expf(-fabsf(x))); }
-__global__ __launch_bounds__(256) void k_loss_partial(const float* bef, const float* aft, const float* stop,
-                                                      const float* tgt, const int* lens, float* scratch, int B, int T,
-                                                      int C, float pw) {
-    // grid (x, B): one wave per frame of utterance blockIdx.y, strided over x; block-level sums, then 4 atomics per
-    // workgroup (bef, aft, stop, per-sample aft) -- same-address atomics serialise, so keep them to a few hundred
-    __shared__ float sh[4];
-    const int lane = threadIdx.x & 63, b = blockIdx.y;
-    const int len = min(lens[b], T);
-    float tb = 0.f, ta = 0.f, tc = 0.f;
-    for (int t = blockIdx.x * 4 + (threadIdx.x >> 6); t < len; t += gridDim.x * 4) {
-        const long row = (long)b * T + t;
-        float sb = 0.f, sa = 0.f;
-        for (int c = lane; c < C; c += 64) {
-            float y = tgt[row * C + c];
-            float d1 = bef[row * C + c] - y, d2 = aft[row * C + c] - y;
-            sb += d1 * d1; sa += d2 * d2;
-        }
-        tb += sb; ta += sa;                       // lanes keep their partial sums; reduced once at the end
-        if (lane == 0) {
-            float x = stop[row];
-            tc += (t == len - 1) ? pw * softplusf(-x) : softplusf(x);
-        }
-    }
-    tb = block_sum_256(tb, sh) / C;
-    ta = block_sum_256(ta, sh) / C;
-    tc = block_sum_256(tc, sh);
-    if (threadIdx.x == 0) {
-        atomicAdd(scratch + 0, tb); atomicAdd(scratch + 1, ta); atomicAdd(scratch + 2, tc);
-        atomicAdd(scratch + 3 + b, ta);
-    }
-}
-// The same sums, vectorised: the valid frames of an utterance are one contiguous prefix of len * C floats of its [T, C] block, so the squared
-// errors stream as float4 with four independent positions per thread in flight (the kernel above walks rows one dependent round trip at a time)
+// Partial sums of the three loss terms, grid (x, B): the valid frames of utterance blockIdx.y are one contiguous prefix of len * C floats of its
+// [T, C] block (C % 4 == 0: ro_loss_fwd), so the squared errors stream as float4 with four independent positions per thread in flight; block-level
+// sums, then at most 4 atomics per workgroup (bef, aft, stop, per-sample aft) -- same-address atomics serialise, so keep them to a few hundred
 __global__ __launch_bounds__(256) void k_loss_partial_v(const float* __restrict__ bef, const float* __restrict__ aft, const float* __restrict__ stop,
                                                         const float* __restrict__ tgt, const int* __restrict__ lens, float* scratch, int T, int C, float pw) {
     __shared__ float sh[4];
@@ -992,55 +962,7 @@ __device__ __forceinline__ float adam_elem(float& p, float g_raw, float& m, floa
     p -= step * m / (sqrtf(v) / sbc2 + eps);
     return p * p;
 }
-__global__ __launch_bounds__(256) void k_mt_adam(const MtChunk* ch, AdamHyper hp, float b1, float b2, float eps,
-                                                 float l2, float gs, float* sumsq_part) {
-    __shared__ float sh[4];
-    const MtChunk c = ch[blockIdx.x];
-    const float lr = hp.lr, bc1 = hp.bc1, sbc2 = hp.sbc2;     // sbc2 = sqrt(1 - beta2^t)
-    const float step = lr / bc1, l2p = c.pad ? l2 : 0.f;
-    float ss = 0.f;
-    int i0 = 0;
-    // 16-byte accesses where the chunk allows it (plain tensors whose four streams are 16-byte aligned): 30 bytes per parameter is all
-    // this kernel does, and dword accesses leave ~10 % of the HBM rate on the table
-    const bool vec = !c.cin && ((((size_t)c.a | (size_t)c.b | (size_t)c.c | (size_t)c.d) & 15) == 0) && (((size_t)c.s & 7) == 0);
-    if (vec) {
-        const int n4 = c.n >> 2;
-        for (int i = threadIdx.x; i < n4; i += 256) {
-            float4 p = reinterpret_cast<const float4*>(c.a)[i], m = reinterpret_cast<const float4*>(c.c)[i], v = reinterpret_cast<const float4*>(c.d)[i];
-            const float4 g = reinterpret_cast<const float4*>(c.b)[i];
-            ss += adam_elem(p.x, g.x, m.x, v.x, gs, l2p, b1, b2, step, sbc2, eps);
-            ss += adam_elem(p.y, g.y, m.y, v.y, gs, l2p, b1, b2, step, sbc2, eps);
-            ss += adam_elem(p.z, g.z, m.z, v.z, gs, l2p, b1, b2, step, sbc2, eps);
-            ss += adam_elem(p.w, g.w, m.w, v.w, gs, l2p, b1, b2, step, sbc2, eps);
-            reinterpret_cast<float4*>(c.c)[i] = m; reinterpret_cast<float4*>(c.d)[i] = v; reinterpret_cast<float4*>(c.a)[i] = p;
-            if (c.s) {                                   // refresh the compute-dtype shadow in the same pass
-                uint2 o;
-                o.x = (uint32_t)f2bf(p.x) | ((uint32_t)f2bf(p.y) << 16);
-                o.y = (uint32_t)f2bf(p.z) | ((uint32_t)f2bf(p.w) << 16);
-                reinterpret_cast<uint2*>(c.s)[i] = o;
-            }
-        }
-        i0 = n4 << 2;
-    }
-    for (int i = i0 + threadIdx.x; i < c.n; i += 256) {
-        float p = c.a[i], m = c.c[i], v = c.d[i];
-        ss += adam_elem(p, c.b[i], m, v, gs, l2p, b1, b2, step, sbc2, eps);
-        c.c[i] = m; c.d[i] = v;
-        c.a[i] = p;
-        if (c.cin) {                                     // conv weight: both re-laid-out images, no separate relayout pass
-            const long gi = c.off + i, r = gi / 5;
-            const int j = (int)(gi - r * 5), co = (int)(r / c.cin), ci = (int)(r - (long)co * c.cin);
-            const bf16_t pb = f2bf(p);
-            c.s[(long)co * 5 * c.cin + (long)j * c.cin + ci] = pb;
-            c.s2[(long)ci * 5 * c.cout + (long)(4 - j) * c.cout + co] = pb;
-        } else if (c.s) c.s[i] = f2bf(p);
-    }
-    if (sumsq_part) {            // sum of squares of the UPDATED L2 members: the next step's regulariser value for free
-        ss = block_sum_256(ss, sh);
-        if (threadIdx.x == 0) sumsq_part[blockIdx.x] = c.pad ? ss : 0.f;
-    }
-}
-// Second form of the same update (default; B2S_ADAM_V1 selects the one above): the chunk kind (no shadow / bf16 shadow / conv images) is
+// The fused multi-tensor update (k_mt_adam2 below is the only form): the chunk kind (no shadow / bf16 shadow / conv images) is
 // workgroup-uniform, so each kind gets its own straight-line loop -- a store under a condition makes the compiler wait for ALL outstanding
 // memory operations at the join (s_waitcnt vmcnt(0)), which serialised every iteration's loads behind the previous iteration's stores --
 // and four float4 iterations of loads are in flight before the first is used.
@@ -1455,13 +1377,10 @@ int ro_bn_bwd(int dtype, const void* dout, int dout_fp32, const float* y, const 
 int ro_loss_fwd(const float* bef, const float* aft, const float* stop, const float* tgt, const int* lens,
                 const float* l2, float* out, float* aft_losses, int B, int T, int C, float pos_weight, float* scratch,
                 hipStream_t st, bool scratch_zeroed) {
+    B2S_CHECK(C % 4 == 0, "loss: C=%d must be a multiple of 4 (the squared errors are read as float4)", C);
     if (!scratch_zeroed) B2S_HIP(hipMemsetAsync(scratch, 0, sizeof(float) * (3 + B), st));
-    if (C % 4 == 0)
-        hipLaunchKernelGGL(k_loss_partial_v, dim3(std::max(1, std::min(cdiv((long)T * C / 4, 1024), 16)), B), dim3(256), 0, st, bef, aft, stop, tgt, lens,
-                           scratch, T, C, pos_weight);
-    else
-        hipLaunchKernelGGL(k_loss_partial, dim3(std::min(cdiv(T, 4), 32), B), dim3(256), 0, st, bef, aft, stop, tgt, lens, scratch, B,
-                           T, C, pos_weight);
+    hipLaunchKernelGGL(k_loss_partial_v, dim3(std::max(1, std::min(cdiv((long)T * C / 4, 1024), 16)), B), dim3(256), 0, st, bef, aft, stop, tgt, lens,
+                       scratch, T, C, pos_weight);
     hipLaunchKernelGGL(k_loss_finalize, dim3(1), dim3(64), 0, st, (const float*)scratch, lens, l2, out, aft_losses, B);
     B2S_LAUNCH_CHECK(); return 0;
 }
@@ -1482,12 +1401,9 @@ int ro_mt_axpy(const MtChunk* chunks, int nchunks, float alpha, const float* gsc
 }
 int ro_mt_adam(const MtChunk* chunks, int nchunks, AdamHyper hp, float beta1, float beta2, float eps, float l2,
                float grad_scale, float* sumsq_part, hipStream_t st, const void* wire, const float* gbase, int max_wg) {
-    constexpr bool v1 = false;
     const int grid = max_wg > 0 ? std::min(max_wg, nchunks) : nchunks;
     if (nchunks > 0 && wire)
         hipLaunchKernelGGL(k_mt_adam2<true>, dim3(grid), dim3(256), 0, st, chunks, nchunks, hp, beta1, beta2, eps, l2, grad_scale, sumsq_part, (const bf16_t*)wire, gbase);
-    else if (nchunks > 0 && v1)
-        hipLaunchKernelGGL(k_mt_adam, dim3(nchunks), dim3(256), 0, st, chunks, hp, beta1, beta2, eps, l2, grad_scale, sumsq_part);
     else if (nchunks > 0)
         hipLaunchKernelGGL(k_mt_adam2<false>, dim3(grid), dim3(256), 0, st, chunks, nchunks, hp, beta1, beta2, eps, l2, grad_scale, sumsq_part, (const bf16_t*)nullptr,
                            (const float*)nullptr);

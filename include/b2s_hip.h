@@ -173,7 +173,10 @@ int b2s_gemm_set_tile_policy(int policy);
 
 /* ---- compute_loss (tacotron.py:136-158) ------------------------------------------------------------
  * losses_out[7] = loss, bef_loss, aft_loss, mse_loss, l2, stop_loss, sum(lengths); aft_losses_out[B].
- * scratch: >= (4 + B) floats. */
+ * scratch: >= (4 + B) floats; its contents on entry do not matter (the call clears what it accumulates into).
+ * Length contract of both calls: 1 <= target_lengths[b] <= T for every b.  Outside it the three kernels disagree: the partial sums clamp a length to T,
+ * while the finalize kernel (the divisions by sum(lengths) and lengths[b]) and the backward kernel (1 / sum(lengths), the stop frame at length - 1)
+ * use the length as given; a length of 0 divides aft_losses_out[b] by zero.  Lengths outside the contract are not tested. */
 int b2s_loss_forward(b2s_model* m, const float* mel_bef, const float* mel_aft, const float* stop_logits,
                      const float* mel_targets, const int32_t* target_lengths, int B, int T, float* losses_out,
                      float* aft_losses_out, float* scratch, void* stream);

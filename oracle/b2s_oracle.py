@@ -313,9 +313,10 @@ def compute_loss(P, cfg, mel_targets, target_lengths, outputs, input_lengths=Non
     aft = mask_reduce(aft_e, target_lengths)
     l2 = cfg.reg_weight * sum((p ** 2).sum() / 2 for n, p in P.items() if is_parameter(n) and l2_member(n))
     T = mel_targets.shape[1]
-    stop_target = (torch.arange(T)[None, :] == target_lengths[:, None] - 1).float()
+    dt = outputs["stop_logits"].dtype        # (fp32 in every fp32 caller; a float64 caller gets a float64 cross entropy, not one rounded to fp32)
+    stop_target = (torch.arange(T)[None, :] == target_lengths[:, None] - 1).to(dt)
     ce = F.binary_cross_entropy_with_logits(outputs["stop_logits"], stop_target, reduction="none",
-                                            pos_weight=torch.tensor([5.0]))
+                                            pos_weight=torch.tensor([5.0], dtype=dt))
     ce = mask_reduce(ce, target_lengths)
     res = {"loss": bef + aft + l2 + ce, "bef_loss": bef, "aft_loss": aft, "aft_losses": aft_s,
            "mse_loss": (bef + aft) / 2, "l2": l2, "stop_loss": ce}

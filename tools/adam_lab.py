@@ -25,4 +25,4 @@ for i in range(N): step(5 + i)
 e1.record(); torch.cuda.synchronize()
 us = e0.elapsed_time(e1) / N * 1e3
 n = eng._gflat.numel()
-print("adam %s: %.1f us per step, %d params, %.2f TB/s (30 B/param)" % ("v1" if os.environ.get("B2S_ADAM_V1") else "v2", us, n, n * 30 / us / 1e6))
+print("adam: %.1f us per step, %d params, %.2f TB/s (30 B/param)" % (us, n, n * 30 / us / 1e6))
