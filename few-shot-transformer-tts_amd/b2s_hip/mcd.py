@@ -1,0 +1,366 @@
+"""ctypes binding of libb2s_mcd.so (C ABI in include/b2s_mcd.h): mel-cepstral distortion after DTW (MCD-DTW, in dB) on the GPU.
+
+The objective score that TTS papers report, from the two things a finished eval already has: the generated mels and the ground
+truth of mels.zip.  Per pair (DESIGN.md section k): voiced frames of each side (the reference's rule in calculate_mse_dtw: max over
+the bins > 0), normalised mel -> natural-log magnitude in fp64, rows 1..order of the orthonormal DCT-II over the mel bins (c_0, the
+energy, is not used), fp32 cepstra, the batched FastDTW of b2s_hip.metrics on them (euclidean, radius 1 by default, radius=None the
+exact dtw), then the mean over the path of 10 / ln 10 * sqrt(2 * sum_k (cx_k - cy_k)^2).  Bit-reproducible, and the same bits for a
+pair alone or inside a batch.  There is no CPU fallback: a missing library is an error.
+
+    python -m b2s_hip.mcd EVAL_DIR --data-dir DATA_DIR [--zipfilepath Z] [--eval-meta M] [--order 13] [--radius 1|exact]
+                          [--batch 64] [--json OUT]
+
+re-scores a finished eval: every EVAL_DIR/<name>.npy against member <name>.npy of mels.zip.
+"""
+import ctypes as C
+import json
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import metrics
+from .lib import B2SError
+from .metrics import _as_batch, _c_radius, _device, _lengths, _pack
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(os.path.dirname(_HERE), "libb2s_mcd.so")
+
+OK, EMPTY, FAILED = 0, 1, 2
+MAX_MELS, MAX_ORDER = 512, 256
+LN_SCALE = math.log(10.0) / 20.0           # dB -> natural-log magnitude
+DB_SCALE = 10.0 / math.log(10.0)           # the MCD's 10 / ln 10
+
+P = C.c_void_p
+_I = C.c_int
+_D = C.c_double
+_PROTOS = {
+    "b2s_mcd_version": (C.c_int, []),
+    "b2s_mcd_last_error": (C.c_char_p, []),
+    "b2s_mcd_ws_bytes": (C.c_size_t, [_I, _I]),
+    "b2s_mcd_cepstra": (C.c_int, [P, P, _I, _I, _I, _I, _I, P, _I, _D, _D, _D, _D, P, P, P, P, P, C.c_size_t, P]),
+    "b2s_mcd_score": (C.c_int, [P, P, _I, P, P, _I, _I, _I, P, P, _I, P, P, _D, P, P, P, P]),
+}
+EXPORTS = sorted(_PROTOS)
+
+_lib = None
+
+
+def load():
+    """Load libb2s_mcd.so (raises B2SError if it is missing -- there is no fallback path)."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise B2SError("libb2s_mcd.so not found at %s -- build it with few-shot-transformer-tts_amd/csrc/build.sh "
+                       "(or __graft_entry__.build()); there is no CPU fallback" % LIB_PATH)
+    lib = C.CDLL(LIB_PATH)
+    for name, (res, args) in _PROTOS.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _lib = lib
+    return lib
+
+
+def check(rc):
+    if rc != 0:
+        raise B2SError(load().b2s_mcd_last_error().decode("utf-8", "replace"))
+
+
+def dct_table(n_mels, order):
+    """Rows 1..order of the orthonormal DCT-II over n_mels bins, float64 [order, n_mels]:
+    D[k, m] = sqrt(2 / n_mels) * cos(pi / n_mels * (m + 0.5) * k).  Computed once here and handed to the kernel as data."""
+    n_mels, order = int(n_mels), int(order)
+    if not 2 <= n_mels <= MAX_MELS:
+        raise B2SError("n_mels must be in 2..%d (got %d)" % (MAX_MELS, n_mels))
+    if not 1 <= order <= min(n_mels - 1, MAX_ORDER):
+        raise B2SError("order must be in 1..%d for %d mel bins (got %d)" % (min(n_mels - 1, MAX_ORDER), n_mels, order))
+    k = np.arange(1, order + 1, dtype=np.float64)[:, None]
+    m = np.arange(n_mels, dtype=np.float64)[None, :]
+    return np.sqrt(2.0 / n_mels) * np.cos(np.pi / n_mels * (m + 0.5) * k)
+
+
+_tables = {}
+
+
+def _device_table(n_mels, order, device):
+    key = (n_mels, order, str(device))
+    if key not in _tables:
+        _tables[key] = torch.from_numpy(dct_table(n_mels, order)).to(device)
+    return _tables[key]
+
+
+def _hp(hp):
+    if hp is None:
+        from hyperparams import hparams as hp
+    return hp
+
+
+def _ptr(t):
+    return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+
+
+def cepstra_packed(rows, offsets, max_len, order=13, hp=None):
+    """b2s_mcd_cepstra on packed device rows [total, n_mels] fp32 with their B + 1 int32 device offsets; max_len bounds every length.
+    No host read.  Returns device tensors: cep (a buffer of `total` rows of which the first offsets[B] are written), offsets
+    [B + 1], voiced [B] and status [B]."""
+    lib = load()
+    hp = _hp(hp)
+    device = rows.device
+    total, n_mels = int(rows.shape[0]), int(rows.shape[1])
+    B = int(offsets.numel()) - 1
+    order = int(order)
+    table = _device_table(n_mels, order, device)               # refuses a bad n_mels / order
+    nbytes = lib.b2s_mcd_ws_bytes(B, int(max_len))
+    if nbytes == 0:
+        check(1)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    cep = torch.empty(total, order, dtype=torch.float32, device=device)
+    off = torch.empty(B + 1, dtype=torch.int32, device=device)
+    voiced = torch.empty(B, dtype=torch.int32, device=device)
+    status = torch.empty(B, dtype=torch.int32, device=device)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    check(lib.b2s_mcd_cepstra(_ptr(rows), _ptr(offsets), total, int(max_len), B, n_mels, order, _ptr(table),
+                              1 if hp.symmetric_mel else 0, float(hp.max_abs_value), float(hp.max_db), float(hp.ref_db), LN_SCALE,
+                              _ptr(cep), _ptr(off), _ptr(voiced), _ptr(status), _ptr(ws), nbytes, stream))
+    return {"cep": cep, "offsets": off, "voiced": voiced, "status": status}
+
+
+def score_packed(cep_x, offsets_x, total_x, cep_y, offsets_y, total_y, path, path_offsets, path_len, dtw_status):
+    """b2s_mcd_score on what cepstra_packed and b2s_met_dtw left on the device: the two cepstral buffers with their B + 1 offsets
+    and host totals, path [total_path, 2] int32 with its B + 1 device offsets, path_len [B] and the DTW's status [B].  No host read.
+    Returns device tensors: mcd [B] f64, status [B] int32 and dist [total_path] f64 (NaN where no step was written)."""
+    lib = load()
+    device = cep_x.device
+    B, order, tp = int(path_len.numel()), int(cep_x.shape[1]), int(path.shape[0])
+    mcd = torch.empty(B, dtype=torch.float64, device=device)
+    status = torch.empty(B, dtype=torch.int32, device=device)
+    dist = torch.full((tp,), float("nan"), dtype=torch.float64, device=device)
+    check(lib.b2s_mcd_score(_ptr(cep_x), _ptr(offsets_x), int(total_x), _ptr(cep_y), _ptr(offsets_y), int(total_y), B, order,
+                            _ptr(path), _ptr(path_offsets), tp, _ptr(path_len), _ptr(dtw_status), DB_SCALE, _ptr(mcd), _ptr(status),
+                            _ptr(dist), torch.cuda.current_stream(device).cuda_stream))
+    return mcd, status, dist
+
+
+def pack_batch(mels, lengths, device=None, what="mels"):
+    """Padded [B, T, n_mels] NumPy array or tensor on any device -> (packed fp32 device rows [sum(lengths), n_mels], their B + 1
+    int32 device offsets, the longest length): what cepstra_packed takes."""
+    t = _as_batch(mels, _pick_device(mels) if device is None else device, what)
+    if int(t.shape[0]) == 0:
+        raise B2SError("%s holds no utterance" % what)
+    n = _lengths(lengths, int(t.shape[0]), int(t.shape[1]), what + "_lengths")
+    rows, off = _pack(t, n)
+    return rows, torch.from_numpy(off).to(t.device), max(n)
+
+
+def _pick_device(*arrays):
+    for a in arrays:
+        if isinstance(a, torch.Tensor) and a.is_cuda:
+            return a.device
+    return _device()
+
+
+def _raise_failed(status, what):
+    bad = np.nonzero(np.asarray(status) == FAILED)[0]
+    if len(bad):
+        raise B2SError("%s failed for utterances %s (offsets inconsistent with the sizes)" % (what, bad.tolist()))
+
+
+def cepstra_batch(mels, lengths, order=13, hp=None):
+    """Voiced frames of every utterance as mel cepstra c_1..c_order.  mels: padded [B, T, n_mels] NumPy array or tensor on any device
+    (normalised mel scale), lengths [B].  Returns device tensors: the cepstra of the whole batch packed gap-free [total_voiced,
+    order] fp32, their B + 1 int32 offsets, and the voiced counts [B] int32.  One host read (offsets and status) sizes the result."""
+    rows, off_d, max_len = pack_batch(mels, lengths)
+    out = cepstra_packed(rows, off_d, max_len, order, hp)
+    host = torch.cat([out["offsets"], out["status"]]).cpu().numpy()
+    B = len(host) // 2
+    _raise_failed(host[B + 1:], "cepstra")
+    return out["cep"][:int(host[B])], out["offsets"], out["voiced"]
+
+
+def mcd_dtw_details(preds, pred_lengths, targets, target_lengths, order=13, radius=1, hp=None):
+    """Everything one scoring call produces, as a dict of device tensors (host where noted): mcd [B] f64 (NaN unless status is OK),
+    status [B] int32 (OK / EMPTY / FAILED, nothing raised here), voiced_x / voiced_y [B], path_len [B], path [sum, 2] int32 with the
+    host array path_offsets [B + 1], dist [sum] f64 (the per-step distortion in dB, laid out like the path), cep_x / cep_y with
+    offsets_x / offsets_y.  The two B + 1 voiced-offset arrays are read back once in the middle of the call (the DTW entry point takes
+    its totals and maxima from the host); everything else is queued on the current stream."""
+    met = metrics.load()
+    device = _pick_device(preds, targets)
+    xr, xo_d, mx = pack_batch(preds, pred_lengths, device, "preds")
+    yr, yo_d, my = pack_batch(targets, target_lengths, device, "targets")
+    B, By = int(xo_d.numel()) - 1, int(yo_d.numel()) - 1
+    if B != By:
+        raise B2SError("preds has %d utterances, targets has %d" % (B, By))
+    if int(xr.shape[1]) != int(yr.shape[1]):
+        raise B2SError("preds has %d mel bins, targets has %d" % (int(xr.shape[1]), int(yr.shape[1])))
+    r = _c_radius(radius)
+    order = int(order)
+    cx = cepstra_packed(xr, xo_d, mx, order, hp)
+    cy = cepstra_packed(yr, yo_d, my, order, hp)
+    host = torch.stack([cx["offsets"], cy["offsets"]]).cpu().numpy()           # the one host read in front of the DTW
+    vx, vy = np.diff(host[0]), np.diff(host[1])
+    tx, ty, vmx, vmy = int(host[0, -1]), int(host[1, -1]), int(vx.max()), int(vy.max())
+    po = np.zeros(B + 1, dtype=np.int32)
+    np.cumsum(vx + vy, out=po[1:])
+    tp = int(po[-1])
+    po_d = torch.from_numpy(po).to(device)
+    nbytes = met.b2s_met_dtw_ws_bytes(B, tx, ty, vmx, vmy, order, r, 0)
+    if nbytes == 0:
+        metrics.check(1)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    cost = torch.empty(B, dtype=torch.float64, device=device)
+    mse = torch.empty(B, dtype=torch.float64, device=device)
+    plen = torch.empty(B, dtype=torch.int32, device=device)
+    dstat = torch.empty(B, dtype=torch.int32, device=device)
+    path = torch.empty(max(1, tp), 2, dtype=torch.int32, device=device)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    metrics.check(met.b2s_met_dtw(_ptr(cx["cep"]), _ptr(cx["offsets"]), tx, vmx, _ptr(cy["cep"]), _ptr(cy["offsets"]), ty, vmy, B,
+                                  order, r, 0, _ptr(cost), _ptr(mse), _ptr(plen), _ptr(dstat), _ptr(path), _ptr(po_d), _ptr(ws),
+                                  nbytes, stream))
+    mcd, sstat, dist = score_packed(cx["cep"], cx["offsets"], tx, cy["cep"], cy["offsets"], ty, path, po_d, plen, dstat)
+    failed = (cx["status"] == FAILED) | (cy["status"] == FAILED)
+    status = torch.where(failed, torch.full_like(sstat, FAILED), sstat)
+    mcd = torch.where(status == OK, mcd, torch.full_like(mcd, float("nan")))
+    return {"mcd": mcd, "status": status, "voiced_x": cx["voiced"], "voiced_y": cy["voiced"], "path_len": plen, "path": path,
+            "path_offsets": po, "path_offsets_device": po_d, "dtw_status": dstat, "dist": dist, "dtw_cost": cost, "cep_x": cx["cep"][:tx], "cep_y": cy["cep"][:ty],
+            "offsets_x": cx["offsets"], "offsets_y": cy["offsets"]}
+
+
+def mcd_dtw_batch(preds, pred_lengths, targets, target_lengths, order=13, radius=1, hp=None, return_paths=False):
+    """MCD-DTW in dB of every pair, as a float64 device tensor [B]; NaN where a side has no voiced frame (status EMPTY).  preds,
+    targets: padded [B, T, n_mels] NumPy arrays or tensors on any device, in the normalised mel scale of `hp` (default: the global
+    hyper-parameters).  radius >= 1 is fastdtw's radius, None the exact dtw.  With return_paths also the list of int64 [L_b, 2] host
+    paths over the voiced frames.  Raises B2SError when a pair FAILED.  Two host reads: the two B + 1 voiced-offset arrays in front of
+    the DTW (it needs host totals and maxima) and, because a FAILED pair has to raise, the B status words at the end.  An empty batch
+    gives an empty tensor."""
+    if len(preds) == 0:
+        empty = torch.empty(0, dtype=torch.float64, device=_pick_device(preds, targets))
+        return (empty, []) if return_paths else empty
+    out = mcd_dtw_details(preds, pred_lengths, targets, target_lengths, order=order, radius=radius, hp=hp)
+    _raise_failed(out["status"].cpu().numpy(), "MCD after DTW")
+    return (out["mcd"], metrics._paths(out)) if return_paths else out["mcd"]
+
+
+def calculate_mcd_dtw(preds, pred_lengths, targets, target_lengths, order=13, radius=1, hp=None):
+    """The list shape of calculate_mse_dtw: one Python float (dB) per pair, None where a side has no voiced frame."""
+    if len(preds) == 0:
+        return []
+    m = mcd_dtw_batch(preds, pred_lengths, targets, target_lengths, order=order, radius=radius, hp=hp).cpu().numpy()
+    return [None if np.isnan(v) else float(v) for v in m]
+
+
+# ------------------------------------------------------------------------------------------------------- re-scoring a finished eval
+
+def _pad(mels, names, n_mels, what):
+    """Ragged list of [T, n_mels] arrays -> padded fp32 [B, max T, n_mels] and the lengths; a file of another shape is a B2SError
+    that names it."""
+    for m, name in zip(mels, names):
+        if m.ndim != 2 or int(m.shape[1]) != n_mels:
+            raise B2SError("%s %s.npy has shape %s, expected [frames, %d]" % (what, name, tuple(m.shape), n_mels))
+    n = [int(m.shape[0]) for m in mels]
+    out = np.zeros((len(mels), max(max(n), 1), n_mels), np.float32)
+    for i, m in enumerate(mels):
+        out[i, :n[i]] = m
+    return out, n
+
+
+def score_eval_dir(eval_dir, zipfilepath, eval_meta=None, order=13, radius=1, batch=64, hp=None):
+    """Score every `<name>.npy` of eval_dir against member `<name>.npy` of the mels.zip, `batch` pairs per GPU call (only one
+    batch of mels is in memory at a time).  Returns the summary dict: overall and per-language mean MCD over the scored records, the
+    counts (scored, empty, without a target) and the per-record scores."""
+    from . import corpus
+    hp = _hp(hp)
+    batch = max(1, int(batch))
+    lang = {}
+    if eval_meta and os.path.exists(eval_meta):
+        for row in corpus.read_metadata(eval_meta, hp.data_format):
+            lang[row["n"][:-4] if row["n"].endswith(".npy") else row["n"]] = row["i"]
+    names = sorted(f[:-4] for f in os.listdir(eval_dir) if f.endswith(".npy"))
+    mels = corpus.MelZip(zipfilepath)
+    records, no_target = [], []
+
+    def score(part, truth):
+        n_mels = int(truth[0].shape[-1])
+        targets, tl = _pad(truth, part, n_mels, "target")
+        preds, pl = _pad([np.load(os.path.join(eval_dir, n + ".npy")).astype(np.float32) for n in part], part, n_mels, "generated")
+        out = mcd_dtw_details(preds, pl, targets, tl, order=order, radius=radius, hp=hp)
+        host = {k: out[k].cpu().numpy() for k in ("mcd", "status", "voiced_x", "voiced_y", "path_len")}
+        _raise_failed(host["status"], "MCD after DTW")
+        for j, n in enumerate(part):
+            empty = int(host["status"][j]) == EMPTY
+            records.append({"name": n, "language": lang.get(n), "mcd": None if empty else float(host["mcd"][j]),
+                            "voiced_pred": int(host["voiced_x"][j]), "voiced_target": int(host["voiced_y"][j]),
+                            "path_len": int(host["path_len"][j])})
+    try:
+        part, truth = [], []
+        for n in names:
+            try:
+                truth.append(mels.load(n + ".npy").astype(np.float32))
+            except KeyError:                                   # generated, but not a member of the zip
+                no_target.append(n)
+                continue
+            part.append(n)
+            if len(part) == batch:
+                score(part, truth)
+                part, truth = [], []
+        if part:
+            score(part, truth)
+    finally:
+        mels.close()
+    scored = [r for r in records if r["mcd"] is not None]
+    languages = {}
+    for r in scored:
+        languages.setdefault(str(r["language"]), []).append(r["mcd"])
+    return {"metric": "mcd_dtw_db", "order": int(order), "radius": "exact" if radius is None else int(radius),
+            "n_scored": len(scored), "n_empty": len(records) - len(scored), "n_without_target": len(no_target),
+            "mcd": float(np.mean([r["mcd"] for r in scored])) if scored else None,
+            "languages": {k: {"n": len(v), "mcd": float(np.mean(v))} for k, v in sorted(languages.items())},
+            "without_target": no_target, "records": records}
+
+
+def main(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m b2s_hip.mcd", description="Re-score a finished eval with MCD-DTW on the GPU.")
+    ap.add_argument("eval_dir", help="directory of generated mels, <name>.npy as save_eval_results writes them")
+    ap.add_argument("--data-dir", required=True, help="directory of mels.zip and metadata.eval.txt")
+    ap.add_argument("--zipfilepath", help="the ground-truth mels (default: DATA_DIR/mels.zip)")
+    ap.add_argument("--eval-meta", help="metadata with the languages (default: DATA_DIR/metadata.eval.txt)")
+    ap.add_argument("--order", type=int, default=13, help="cepstral coefficients c_1..c_order")
+    ap.add_argument("--radius", default="1", help="fastdtw radius >= 1, or 'exact' for the full dtw")
+    ap.add_argument("--batch", type=int, default=64, help="pairs per GPU call")
+    ap.add_argument("--json", metavar="OUT", help="also write the summary, with the per-record scores, to OUT")
+    a = ap.parse_args(argv)
+    zipfilepath = a.zipfilepath or os.path.join(a.data_dir, "mels.zip")
+    eval_meta = a.eval_meta or os.path.join(a.data_dir, "metadata.eval.txt")
+    try:
+        radius = None if a.radius == "exact" else int(a.radius)
+    except ValueError:
+        radius = 0
+    if radius is not None and radius < 1:
+        print("--radius must be an integer >= 1 or 'exact' (got %r)" % a.radius, file=sys.stderr)
+        return 2
+    from hyperparams import hparams as hp
+    top = min(int(hp.num_mels) - 1, MAX_ORDER)
+    if not 1 <= a.order <= top:
+        print("--order must be in 1..%d for %d mel bins (got %d)" % (top, int(hp.num_mels), a.order), file=sys.stderr)
+        return 2
+    if a.batch < 1:
+        print("--batch must be >= 1 (got %d)" % a.batch, file=sys.stderr)
+        return 2
+    for what, path, ok in (("EVAL_DIR", a.eval_dir, os.path.isdir(a.eval_dir)), ("mels.zip", zipfilepath, os.path.isfile(zipfilepath))):
+        if not ok:
+            print("%s not found: %s" % (what, path), file=sys.stderr)
+            return 2
+    res = score_eval_dir(a.eval_dir, zipfilepath, eval_meta, order=a.order, radius=radius, batch=a.batch)
+    if a.json:
+        with open(a.json, "w", encoding="utf-8") as f:
+            json.dump(res, f, ensure_ascii=False, indent=1)
+    print(json.dumps({k: v for k, v in res.items() if k not in ("records", "without_target")}, ensure_ascii=False))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

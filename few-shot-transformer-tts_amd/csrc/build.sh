@@ -1,5 +1,5 @@
 #!/bin/bash
-# Build libb2s_hip.so, libb2s_vocoder.so and libb2s_metrics.so for gfx950 (MI355X).  hipcc cross-compiles without a GPU.
+# Build libb2s_hip.so, libb2s_vocoder.so, libb2s_metrics.so and libb2s_mcd.so for gfx950 (MI355X).  hipcc cross-compiles without a GPU.
 #   build.sh            only what changed
 #   build.sh --clean    recompile every source (what __graft_entry__.build() runs)
 #   build.sh --lab      measurement build with -DB2S_LAB (B2S_LAB_* environment switches that change results: skip the encoder, drop the
@@ -37,4 +37,11 @@ if [ "$1" != "--lab" ]; then
     hipcc $FLAGS -shared metrics/dtw.hip metrics/align.hip metrics/edit.hip -o $MOUT
   fi
   echo "built $MOUT"
+  # mel-cepstral distortion after DTW: the cepstral front end and the scoring along the path (include/b2s_mcd.h); contraction off,
+  # the definition rounds every product and sum on its own
+  COUT=../libb2s_mcd.so
+  if [ "$1" = "--clean" ] || [ ! -f $COUT ] || [ mcd/mcd.hip -nt $COUT ] || [ ../../include/b2s_mcd.h -nt $COUT ]; then
+    hipcc $FLAGS -ffp-contract=off -shared mcd/mcd.hip -o $COUT
+  fi
+  echo "built $COUT"
 fi
