@@ -17,18 +17,12 @@ One JSON line is printed.
 """
 import argparse
 import json
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.abspath(__file__))
-PKG = os.path.join(ROOT, "few-shot-transformer-tts_amd")
-for p in (ROOT, PKG, os.path.join(ROOT, "tests")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from benchtime import time_calls
 
 B, L, H, S, T = 64, 6, 8, 256, 1000
 
@@ -48,21 +42,6 @@ def make_layers(t, seed=1234):
 
 def required_bytes(enc, dec, t):
     return sum(L * H * min(e, S) * min(d, t) * 4 for e, d in zip(enc, dec))
-
-
-def time_calls(fn, runs, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(runs):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(min(ms)), float(max(ms))
 
 
 def copy_ms(nbytes, runs, warmup):

@@ -13,18 +13,12 @@ One JSON line is printed.
 """
 import argparse
 import json
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.abspath(__file__))
-PKG = os.path.join(ROOT, "few-shot-transformer-tts_amd")
-for p in (ROOT, PKG, os.path.join(ROOT, "tests")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from benchtime import time_calls
 
 
 def make_batch(B=64, dim=80, seed=1234):
@@ -42,21 +36,6 @@ def make_batch(B=64, dim=80, seed=1234):
         preds[b, :pl[b]] = a
         targets[b, :tl[b]] = c
     return preds, pl, targets, tl
-
-
-def time_calls(fn, runs, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(runs):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(min(ms)), float(max(ms))
 
 
 def cpu_baseline(preds, pl, targets, tl, n=3):

@@ -14,20 +14,14 @@ first 3 pairs on one core and scales it to the batch (labelled as such).  One JS
 """
 import argparse
 import json
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.abspath(__file__))
-PKG = os.path.join(ROOT, "few-shot-transformer-tts_amd")
-for p in (ROOT, PKG, os.path.join(ROOT, "tests")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from benchtime import time_calls
 
-from bench_dtw import make_batch, time_calls  # noqa: E402
+from bench_dtw import make_batch
 
 ORDER = 13
 

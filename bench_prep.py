@@ -17,36 +17,15 @@ kept intervals, C = the cropped samples and O = B * (Lmax + 4000),
 """
 import argparse
 import json
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.abspath(__file__))
-PKG = os.path.join(ROOT, "few-shot-transformer-tts_amd")
-for p in (ROOT, PKG, os.path.join(ROOT, "tests")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from benchtime import time_calls
 
 COPY_GBS = 6300.0             # the copy bandwidth the project measures its memory-bound kernels against
 SR = 16000
-
-
-def time_events(fn, runs, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(runs):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(min(ms)), float(max(ms))
 
 
 def time_wall(fn, runs, warmup):
@@ -108,7 +87,7 @@ def main():
     q_full = [np.asarray(iv) for iv in ivs]
     Vq = sum(int((iv[:, 1] - iv[:, 0]).sum()) for iv in q_full)
 
-    trim = figures(time_events(lambda: prep._trim_device(wavs, lengths, gap), a.runs, a.warmup), trim_bytes, B, S_)
+    trim = figures(time_calls(lambda: prep._trim_device(wavs, lengths, gap), a.runs, a.warmup), trim_bytes, B, S_)
     trim["ms_with_readback"] = round(time_wall(lambda: prep.trim_audios_batch(wavs, lengths, gap), a.runs, a.warmup), 4)
     trim["status_counts"] = [int((status == s).sum()) for s in range(4)]
 
@@ -128,7 +107,7 @@ def main():
         vocoder.check(lib.b2s_voc_prep_abs_quantile(ptr(wavs), ptr(lens_dev), B, Lmax, ptr(iv_dev), ptr(n_dev), NI, 0.95, ptr(q_out),
                                                     ptr(ws_q), ws_q.numel(), torch.cuda.current_stream().cuda_stream))
 
-    quant = figures(time_events(quantile, a.runs, a.warmup), 4 * 3 * Vq, B, S_)
+    quant = figures(time_calls(quantile, a.runs, a.warmup), 4 * 3 * Vq, B, S_)
     want = np.array([P.abs_quantile(w, iv, 0.95) for w, iv in zip(ws, q_full)], np.float32)
     if not np.array_equal(q_out.cpu().numpy().view(np.uint32), want.view(np.uint32)):
         raise RuntimeError("abs_quantile differs from np.sort")

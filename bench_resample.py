@@ -17,36 +17,15 @@ batch needs (per output the two wing counts of the algorithm, edges included).  
 """
 import argparse
 import json
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.abspath(__file__))
-PKG = os.path.join(ROOT, "few-shot-transformer-tts_amd")
-for p in (ROOT, PKG, os.path.join(ROOT, "tests")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from benchtime import time_calls
 
 LDS_BYTES_PER_S = 256.0 * 256 * 2.4e9         # 256 B/clk/CU, 256 CUs, 2.4 GHz
 SR = 16000
-
-
-def time_events(fn, runs, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(runs):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(min(ms)), float(max(ms))
 
 
 def tap_count(n, orig_sr):
@@ -85,13 +64,13 @@ def workload(name, orig_sr, channels, lengths, runs, warmup, rng):
         if n_out[b] != len(ref) or err > bound:
             raise RuntimeError("%s: utterance %d differs from the restatement by %g (bound %g)" % (name, b, err, bound))
         worst = max(worst, err)
-    med, lo, hi = time_events(lambda: prep._resample_device(wavs, lengths, orig_sr), runs, warmup)
+    med, lo, hi = time_calls(lambda: prep._resample_device(wavs, lengths, orig_sr), runs, warmup)
     taps = sum(tap_count(n, orig_sr) for n in lengths)
     outputs = int(sum(prep.resample_lengths(n, orig_sr)[0] for n in lengths))
     moved = 4 * (B * Lmax * channels + out.numel())
     src = torch.empty(moved // 8, dtype=torch.float32, device="cuda")
     dst = torch.empty_like(src)
-    copy_ms = time_events(lambda: dst.copy_(src), runs, warmup)[0]
+    copy_ms = time_calls(lambda: dst.copy_(src), runs, warmup)[0]
     floor_ms = taps * 12 / LDS_BYTES_PER_S * 1e3
     tile, span = prep.resample_tile(orig_sr)
     return {"orig_sr": orig_sr, "channels": channels, "B": B, "Lmax_in": Lmax, "Lmax_out": int(out.shape[1]), "input_s": round(sum(lengths) / orig_sr, 1),

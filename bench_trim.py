@@ -13,36 +13,15 @@ the fp64 NumPy restatement on one utterance of each workload's mean length.  One
 """
 import argparse
 import json
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.abspath(__file__))
-PKG = os.path.join(ROOT, "few-shot-transformer-tts_amd")
-for p in (ROOT, PKG, os.path.join(ROOT, "tests")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from benchtime import time_calls
 
 PEAK_HBM_GBS = 8000.0
 HOP = 200
-
-
-def time_events(fn, runs, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(runs):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(min(ms)), float(max(ms))
 
 
 def time_wall(fn, runs, warmup):
@@ -71,7 +50,7 @@ def workload(name, lengths, runs, warmup, seed):
     def device_only():
         return vocoder._gather_device(vocoder._split_device(wavs, lengths, *params))
 
-    med, lo, hi = time_events(device_only, runs, warmup)
+    med, lo, hi = time_calls(device_only, runs, warmup)
     wall = time_wall(lambda: vocoder.trim_silence_intervals_batch(wavs, lengths), runs, warmup)
     out, out_lens = vocoder.trim_silence_intervals_batch(wavs, lengths)
     want = R.trim_silence_intervals(pad[0, :lengths[0]])

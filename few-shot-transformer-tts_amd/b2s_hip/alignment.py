@@ -14,10 +14,9 @@ import threading
 import numpy as np
 import torch
 
-from . import metrics
-from .lib import B2SError
+from . import metrics, ragged
+from .cbind import B2SError, choice, dptr as p
 
-ALIGN_CHOICES = ("reference", "hip")
 STAT_NAMES = ("backward_steps", "max_jump", "positions_visited", "last_position")
 MAX_LAYERS = 16
 
@@ -26,11 +25,7 @@ _plot_lock = threading.Lock()          # one figure at a time, as in the referen
 
 def mode(hp=None):
     """hp.align, checked: "reference" or "hip"; anything else is a ValueError."""
-    if hp is None:
-        from hyperparams import hparams as hp
-    if hp.align not in ALIGN_CHOICES:
-        raise ValueError("unknown align %r (expected 'reference' or 'hip')" % (hp.align,))
-    return hp.align
+    return choice(hp, "align")
 
 
 def chunk():
@@ -62,8 +57,7 @@ def select_alignments(encdec, input_lengths, generated_lengths, want_maps=True):
     encdec = list(encdec)
     if not 1 <= len(encdec) <= MAX_LAYERS:
         raise B2SError("select_alignments takes 1..%d layers (got %d)" % (MAX_LAYERS, len(encdec)))
-    first = encdec[0]
-    device = first.device if isinstance(first, torch.Tensor) and first.is_cuda else metrics._device()
+    device = ragged.device("the DTW metric", encdec[0])
     layers = []
     for a in encdec:
         t = a.detach() if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))
@@ -73,20 +67,15 @@ def select_alignments(encdec, input_lengths, generated_lengths, want_maps=True):
     B, H, S, T = (int(v) for v in layers[0].shape)
     L = len(layers)
     nbytes = lib.b2s_met_align_ws_bytes(B, L, H, S, T)
-    if nbytes == 0:
-        metrics.check(1)
+    ws = metrics.workspace(nbytes, device)
     enc = _lengths_i32(input_lengths, B, device, "input_lengths")
     dec = _lengths_i32(generated_lengths, B, device, "generated_lengths")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
     scores = torch.empty(B, L, H, dtype=torch.float64, device=device)
     best = torch.empty(B, dtype=torch.int32, device=device)
     maps = torch.empty(B, S, T, dtype=torch.float32, device=device) if want_maps else None
     paths = torch.empty(B, T, dtype=torch.int32, device=device)
     stats = torch.empty(B, 4, dtype=torch.int32, device=device)
     table = (C.c_void_p * L)(*[t.data_ptr() for t in layers])          # host array: the pointers travel in the kernel arguments
-
-    def p(t):
-        return None if t is None else C.c_void_p(t.data_ptr())
     with torch.cuda.device(device):
         stream = torch.cuda.current_stream(device).cuda_stream
         metrics.check(lib.b2s_met_align_select(C.cast(table, C.c_void_p), L, B, H, S, T, p(enc), p(dec), p(scores), p(best), p(maps),

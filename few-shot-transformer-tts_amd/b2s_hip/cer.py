@@ -18,7 +18,6 @@ everything after it is here, without the editdistance package:
 install(hp) binds the `editdistance` global of the reference's utils.transcribe (if imported) to this module for hp.cer == "hip" and
 restores it for "reference"; synthesize.eval_batch calls it.  There is no CPU fallback: a missing library or device is an error.
 """
-import ctypes as C
 import json
 import logging
 import os
@@ -30,10 +29,9 @@ import unicodedata
 import numpy as np
 import torch
 
-from . import metrics
-from .lib import B2SError
+from . import metrics, ragged
+from .cbind import B2SError, choice, dptr as p, rebind
 
-CER_CHOICES = ("reference", "hip")
 OP_NAMES = ("sub", "del", "ins")
 
 _DROPPED = frozenset(("Pc", "Pd", "Ps", "Pe", "Pi", "Pf", "Po"))                  # every punctuation category
@@ -94,16 +92,10 @@ def pack(items, device=None, vocab=None):
     """Host sequences -> Packed on `device` (default: the current HIP device).  `vocab` is the token -> id dict that lists of str
     tokens share; pass the same dict for both sides of a comparison."""
     if device is None:
-        if not torch.cuda.is_available():
-            raise B2SError("the edit distance runs on the GPU only; no HIP device is visible")
-        device = torch.device("cuda", torch.cuda.current_device())
+        device = ragged.device("the edit distance")
     vocab = {} if vocab is None else vocab
     parts = [_symbols(it, vocab) for it in items]
-    off = np.zeros(len(parts) + 1, dtype=np.int64)
-    np.cumsum([len(p) for p in parts], out=off[1:])
-    if off[-1] >= 2 ** 31:
-        raise B2SError("%d symbols in one batch: the offsets are int32" % off[-1])
-    off = off.astype(np.int32)
+    off = ragged.offsets([len(part) for part in parts])
     flat = np.concatenate(parts) if off[-1] else np.zeros(1, dtype=np.int32)
     return Packed(torch.from_numpy(np.ascontiguousarray(flat, dtype=np.int32)).to(device), off, torch.from_numpy(off).to(device))
 
@@ -129,9 +121,6 @@ def _run(a, b, return_ops):
     if n == 0:
         return dist, ops
     status = torch.empty(n, dtype=torch.int32, device=device)
-
-    def p(t):
-        return None if t is None else C.c_void_p(t.data_ptr())
     with torch.cuda.device(device):
         stream = torch.cuda.current_stream(device).cuda_stream
         metrics.check(lib.b2s_met_edit_distance(p(a.symbols), p(a.offsets_d), int(a.offsets[-1]), a.max_len, p(b.symbols),
@@ -245,23 +234,10 @@ _SHIM = types.SimpleNamespace(eval=eval)                 # what utils.transcribe
 def install(hp=None):
     """Bind the `editdistance` global of utils.transcribe (the reference's module, if imported) to this module's eval for
     hp.cer == "hip"; restore the original for "reference".  Anything else is a ValueError."""
-    if hp is None:
-        from hyperparams import hparams as hp
-    mode = hp.cer
-    if mode not in CER_CHOICES:
-        raise ValueError("unknown cer %r (expected 'reference' or 'hip')" % (mode,))
-    mod = sys.modules.get("utils.transcribe")
-    if mod is None or not hasattr(mod, "editdistance"):
-        return
-    bound = mod.editdistance is _SHIM
-    if mode == "hip" and not bound:
-        setattr(mod, _ORIGINAL, mod.editdistance)
-        mod.editdistance = _SHIM
-        logging.info("cer=hip: utils.transcribe scores with the GPU edit distance (b2s_hip.cer)")
-    elif mode == "reference" and bound and hasattr(mod, _ORIGINAL):
-        mod.editdistance = getattr(mod, _ORIGINAL)
-        delattr(mod, _ORIGINAL)
-        logging.info("cer=reference: utils.transcribe.editdistance restored")
+    on = choice(hp, "cer") == "hip"
+    if rebind("utils.transcribe", "editdistance", _SHIM, _ORIGINAL, on):
+        logging.info("cer=hip: utils.transcribe scores with the GPU edit distance (b2s_hip.cer)" if on else
+                     "cer=reference: utils.transcribe.editdistance restored")
 
 
 def main(argv=None):

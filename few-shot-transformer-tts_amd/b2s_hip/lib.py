@@ -18,14 +18,7 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 import torch  # noqa: E402
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("B2S_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "libb2s_hip.so")      # (override: instrumented development builds)
-
-_lib = None
-
-
-class B2SError(RuntimeError):
-    pass
+from .cbind import B2SError, Library  # noqa: E402,F401
 
 
 class Config(C.Structure):
@@ -128,29 +121,8 @@ _PROTOS = {
     "b2s_encf_reduce_layernorm_backward": (C.c_int, [P, C.c_int, C.c_int, P, P, P, P, P, P, P, P, P, C.c_float, C.c_uint64, C.c_uint32, C.c_int, P]),
     "b2s_transpose_bf16": (C.c_int, [P, P, C.c_int, C.c_int, P]),
 }
-EXPORTS = sorted(_PROTOS)
-
-
-def load():
-    """Load libb2s_hip.so (raises B2SError if it is missing -- there is no fallback path)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise B2SError("libb2s_hip.so not found at %s -- build it with few-shot-transformer-tts_amd/csrc/build.sh "
-                       "(or __graft_entry__.build()); there is no CPU fallback" % LIB_PATH)
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in _PROTOS.items():
-        fn = getattr(lib, name)           # AttributeError if the symbol is not exported
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
-    return lib
-
-
-def check(rc):
-    if rc != 0:
-        raise B2SError(load().b2s_last_error().decode("utf-8", "replace"))
+_LIB = Library("libb2s_hip.so", _PROTOS, "b2s_last_error", path=os.environ.get("B2S_LIB_PATH"))     # (override: instrumented development builds)
+LIB_PATH, EXPORTS, load, check = _LIB.path, _LIB.exports, _LIB.load, _LIB.check
 
 
 def ptr(t):

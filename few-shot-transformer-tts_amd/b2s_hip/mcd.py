@@ -21,12 +21,9 @@ import sys
 import numpy as np
 import torch
 
-from . import metrics
-from .lib import B2SError
-from .metrics import _as_batch, _c_radius, _device, _lengths, _pack
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(os.path.dirname(_HERE), "libb2s_mcd.so")
+from . import metrics, ragged
+from .cbind import B2SError, Library, dptr
+from .vocoder import _hp
 
 OK, EMPTY, FAILED = 0, 1, 2
 MAX_MELS, MAX_ORDER = 512, 256
@@ -43,31 +40,8 @@ _PROTOS = {
     "b2s_mcd_cepstra": (C.c_int, [P, P, _I, _I, _I, _I, _I, P, _I, _D, _D, _D, _D, P, P, P, P, P, C.c_size_t, P]),
     "b2s_mcd_score": (C.c_int, [P, P, _I, P, P, _I, _I, _I, P, P, _I, P, P, _D, P, P, P, P]),
 }
-EXPORTS = sorted(_PROTOS)
-
-_lib = None
-
-
-def load():
-    """Load libb2s_mcd.so (raises B2SError if it is missing -- there is no fallback path)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise B2SError("libb2s_mcd.so not found at %s -- build it with few-shot-transformer-tts_amd/csrc/build.sh "
-                       "(or __graft_entry__.build()); there is no CPU fallback" % LIB_PATH)
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in _PROTOS.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
-    return lib
-
-
-def check(rc):
-    if rc != 0:
-        raise B2SError(load().b2s_mcd_last_error().decode("utf-8", "replace"))
+_LIB = Library("libb2s_mcd.so", _PROTOS, "b2s_mcd_last_error")
+LIB_PATH, EXPORTS, load, check, workspace = _LIB.path, _LIB.exports, _LIB.load, _LIB.check, _LIB.workspace
 
 
 def dct_table(n_mels, order):
@@ -93,14 +67,8 @@ def _device_table(n_mels, order, device):
     return _tables[key]
 
 
-def _hp(hp):
-    if hp is None:
-        from hyperparams import hparams as hp
-    return hp
-
-
 def _ptr(t):
-    return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+    return dptr(t, empty_null=True)
 
 
 def cepstra_packed(rows, offsets, max_len, order=13, hp=None):
@@ -115,9 +83,7 @@ def cepstra_packed(rows, offsets, max_len, order=13, hp=None):
     order = int(order)
     table = _device_table(n_mels, order, device)               # refuses a bad n_mels / order
     nbytes = lib.b2s_mcd_ws_bytes(B, int(max_len))
-    if nbytes == 0:
-        check(1)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    ws = workspace(nbytes, device)
     cep = torch.empty(total, order, dtype=torch.float32, device=device)
     off = torch.empty(B + 1, dtype=torch.int32, device=device)
     voiced = torch.empty(B, dtype=torch.int32, device=device)
@@ -148,19 +114,16 @@ def score_packed(cep_x, offsets_x, total_x, cep_y, offsets_y, total_y, path, pat
 def pack_batch(mels, lengths, device=None, what="mels"):
     """Padded [B, T, n_mels] NumPy array or tensor on any device -> (packed fp32 device rows [sum(lengths), n_mels], their B + 1
     int32 device offsets, the longest length): what cepstra_packed takes."""
-    t = _as_batch(mels, _pick_device(mels) if device is None else device, what)
+    t = ragged.as_batch(mels, _pick_device(mels) if device is None else device, what)
     if int(t.shape[0]) == 0:
         raise B2SError("%s holds no utterance" % what)
-    n = _lengths(lengths, int(t.shape[0]), int(t.shape[1]), what + "_lengths")
-    rows, off = _pack(t, n)
+    n = ragged.lengths(lengths, int(t.shape[0]), int(t.shape[1]), what + "_lengths")
+    rows, off = ragged.pack(t, n)
     return rows, torch.from_numpy(off).to(t.device), max(n)
 
 
 def _pick_device(*arrays):
-    for a in arrays:
-        if isinstance(a, torch.Tensor) and a.is_cuda:
-            return a.device
-    return _device()
+    return ragged.device("the DTW metric", *arrays)
 
 
 def _raise_failed(status, what):
@@ -187,7 +150,6 @@ def mcd_dtw_details(preds, pred_lengths, targets, target_lengths, order=13, radi
     host array path_offsets [B + 1], dist [sum] f64 (the per-step distortion in dB, laid out like the path), cep_x / cep_y with
     offsets_x / offsets_y.  The two B + 1 voiced-offset arrays are read back once in the middle of the call (the DTW entry point takes
     its totals and maxima from the host); everything else is queued on the current stream."""
-    met = metrics.load()
     device = _pick_device(preds, targets)
     xr, xo_d, mx = pack_batch(preds, pred_lengths, device, "preds")
     yr, yo_d, my = pack_batch(targets, target_lengths, device, "targets")
@@ -196,36 +158,22 @@ def mcd_dtw_details(preds, pred_lengths, targets, target_lengths, order=13, radi
         raise B2SError("preds has %d utterances, targets has %d" % (B, By))
     if int(xr.shape[1]) != int(yr.shape[1]):
         raise B2SError("preds has %d mel bins, targets has %d" % (int(xr.shape[1]), int(yr.shape[1])))
-    r = _c_radius(radius)
+    r = metrics.c_radius(radius)
     order = int(order)
     cx = cepstra_packed(xr, xo_d, mx, order, hp)
     cy = cepstra_packed(yr, yo_d, my, order, hp)
     host = torch.stack([cx["offsets"], cy["offsets"]]).cpu().numpy()           # the one host read in front of the DTW
     vx, vy = np.diff(host[0]), np.diff(host[1])
     tx, ty, vmx, vmy = int(host[0, -1]), int(host[1, -1]), int(vx.max()), int(vy.max())
-    po = np.zeros(B + 1, dtype=np.int32)
-    np.cumsum(vx + vy, out=po[1:])
-    tp = int(po[-1])
-    po_d = torch.from_numpy(po).to(device)
-    nbytes = met.b2s_met_dtw_ws_bytes(B, tx, ty, vmx, vmy, order, r, 0)
-    if nbytes == 0:
-        metrics.check(1)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    cost = torch.empty(B, dtype=torch.float64, device=device)
-    mse = torch.empty(B, dtype=torch.float64, device=device)
-    plen = torch.empty(B, dtype=torch.int32, device=device)
-    dstat = torch.empty(B, dtype=torch.int32, device=device)
-    path = torch.empty(max(1, tp), 2, dtype=torch.int32, device=device)
-    stream = torch.cuda.current_stream(device).cuda_stream
-    metrics.check(met.b2s_met_dtw(_ptr(cx["cep"]), _ptr(cx["offsets"]), tx, vmx, _ptr(cy["cep"]), _ptr(cy["offsets"]), ty, vmy, B,
-                                  order, r, 0, _ptr(cost), _ptr(mse), _ptr(plen), _ptr(dstat), _ptr(path), _ptr(po_d), _ptr(ws),
-                                  nbytes, stream))
+    dtw = metrics.dtw_packed(cx["cep"], cx["offsets"], tx, vmx, cy["cep"], cy["offsets"], ty, vmy, B, order, r, 0,
+                             ragged.offsets(vx + vy))
+    path, po, po_d, plen, dstat = dtw["path"], dtw["path_offsets"], dtw["path_offsets_device"], dtw["path_len"], dtw["status"]
     mcd, sstat, dist = score_packed(cx["cep"], cx["offsets"], tx, cy["cep"], cy["offsets"], ty, path, po_d, plen, dstat)
     failed = (cx["status"] == FAILED) | (cy["status"] == FAILED)
     status = torch.where(failed, torch.full_like(sstat, FAILED), sstat)
     mcd = torch.where(status == OK, mcd, torch.full_like(mcd, float("nan")))
     return {"mcd": mcd, "status": status, "voiced_x": cx["voiced"], "voiced_y": cy["voiced"], "path_len": plen, "path": path,
-            "path_offsets": po, "path_offsets_device": po_d, "dtw_status": dstat, "dist": dist, "dtw_cost": cost, "cep_x": cx["cep"][:tx], "cep_y": cy["cep"][:ty],
+            "path_offsets": po, "path_offsets_device": po_d, "dtw_status": dstat, "dist": dist, "dtw_cost": dtw["cost"], "cep_x": cx["cep"][:tx], "cep_y": cy["cep"][:ty],
             "offsets_x": cx["offsets"], "offsets_y": cy["offsets"]}
 
 
@@ -241,7 +189,7 @@ def mcd_dtw_batch(preds, pred_lengths, targets, target_lengths, order=13, radius
         return (empty, []) if return_paths else empty
     out = mcd_dtw_details(preds, pred_lengths, targets, target_lengths, order=order, radius=radius, hp=hp)
     _raise_failed(out["status"].cpu().numpy(), "MCD after DTW")
-    return (out["mcd"], metrics._paths(out)) if return_paths else out["mcd"]
+    return (out["mcd"], ragged.paths(out)) if return_paths else out["mcd"]
 
 
 def calculate_mcd_dtw(preds, pred_lengths, targets, target_lengths, order=13, radius=1, hp=None):

@@ -9,20 +9,15 @@ restores the original for "reference"); synthesize.eval_batch calls it, so the u
 """
 import ctypes as C
 import logging
-import os
-import sys
 
 import numpy as np
 import torch
 
-from .lib import B2SError
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(os.path.dirname(_HERE), "libb2s_metrics.so")
+from . import ragged
+from .cbind import B2SError, Library, choice, dptr, rebind
 
 VOICED_ONLY = 1
 OK, EMPTY, FAILED = 0, 1, 2
-MSE_DTW_CHOICES = ("reference", "hip")
 
 P = C.c_void_p
 _I = C.c_int
@@ -39,34 +34,12 @@ _PROTOS = {
     "b2s_met_edit_max_len": (C.c_int, []),
     "b2s_met_edit_distance": (C.c_int, [P, P, _I, _I, P, P, _I, _I, _I, P, P, P, P]),
 }
-EXPORTS = sorted(_PROTOS)
-
-_lib = None
-
-
-def load():
-    """Load libb2s_metrics.so (raises B2SError if it is missing -- there is no fallback path)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise B2SError("libb2s_metrics.so not found at %s -- build it with few-shot-transformer-tts_amd/csrc/build.sh "
-                       "(or __graft_entry__.build()); there is no CPU fallback" % LIB_PATH)
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in _PROTOS.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
-    return lib
+_LIB = Library("libb2s_metrics.so", _PROTOS, "b2s_met_last_error")
+LIB_PATH, EXPORTS, load, check, workspace = _LIB.path, _LIB.exports, _LIB.load, _LIB.check, _LIB.workspace
 
 
-def check(rc):
-    if rc != 0:
-        raise B2SError(load().b2s_met_last_error().decode("utf-8", "replace"))
-
-
-def _c_radius(radius):
+def c_radius(radius):
+    """fastdtw's radius as the C ABI takes it: >= 1, or -1 for None (the exact dtw)."""
     if radius is None:
         return -1
     radius = int(radius)
@@ -75,93 +48,49 @@ def _c_radius(radius):
     return radius
 
 
-def _lengths(lengths, B, T, what):
-    if isinstance(lengths, torch.Tensor):
-        lengths = lengths.detach().cpu().numpy()
-    out = [int(n) for n in np.asarray(lengths).reshape(-1)]
-    if len(out) != B:
-        raise B2SError("%d %s for a batch of %d" % (len(out), what, B))
-    if any(n < 0 for n in out):
-        raise B2SError("%s must be >= 0 (got %s)" % (what, out))
-    return [min(n, T) for n in out]                    # x[i, :n] slices past the end like the reference's indexing
+def dtw_packed(xp, xo_d, tx, mx, yp, yo_d, ty, my, B, dim, r, flags, path_offsets=None):
+    """One b2s_met_dtw call on packed device rows xp [tx, dim] / yp [ty, dim] fp32 with their B + 1 int32 device offsets, the host
+    totals tx / ty and longest lengths mx / my; r from c_radius.  `path_offsets` (B + 1 int32 on the host, each pair's room at least
+    its two lengths summed) asks for the paths.  No host read; queued on the current stream.  Returns device tensors: cost and mse
+    [B] f64, path_len and status [B] int32, and with path_offsets also path [total, 2] int32, path_offsets_device and path_offsets
+    itself (the host array)."""
+    lib = load()
+    device = xo_d.device
+    nbytes = lib.b2s_met_dtw_ws_bytes(B, tx, ty, mx, my, dim, r, flags)
+    ws = workspace(nbytes, device)
+    out = {"cost": torch.empty(B, dtype=torch.float64, device=device), "mse": torch.empty(B, dtype=torch.float64, device=device),
+           "path_len": torch.empty(B, dtype=torch.int32, device=device), "status": torch.empty(B, dtype=torch.int32, device=device)}
+    path = po_d = None
+    if path_offsets is not None:
+        path = out["path"] = torch.empty(max(1, int(path_offsets[-1])), 2, dtype=torch.int32, device=device)
+        po_d = out["path_offsets_device"] = torch.from_numpy(path_offsets).to(device)
+        out["path_offsets"] = path_offsets
 
-
-def _device():
-    if not torch.cuda.is_available():
-        raise B2SError("the DTW metric runs on the GPU only; no HIP device is visible")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _as_batch(a, device, what):
-    """[B, T, dim] (or [B, T] for dim 1) NumPy array or tensor on any device -> contiguous fp32 tensor [B, T, dim] on `device`."""
-    t = torch.from_numpy(np.asarray(a)) if not isinstance(a, torch.Tensor) else a.detach()
-    if t.dim() == 2:
-        t = t.unsqueeze(-1)
-    if t.dim() != 3:
-        raise B2SError("%s must be [B, T, dim] or [B, T], got %s" % (what, tuple(t.shape)))
-    return t.to(device=device, dtype=torch.float32).contiguous()
-
-
-def _pack(t, lengths):
-    """Padded [B, T, dim] -> packed [sum(lengths), dim] rows and B + 1 int32 offsets (host and device)."""
-    B, T = int(t.shape[0]), int(t.shape[1])
-    mask = torch.arange(T).unsqueeze(0) < torch.tensor(lengths, dtype=torch.int64).unsqueeze(1)
-    packed = t[mask.to(t.device)].contiguous()
-    off = np.zeros(B + 1, dtype=np.int32)
-    np.cumsum(lengths, out=off[1:])
-    return packed, off
+    def p(t):
+        return dptr(t, empty_null=True)
+    check(lib.b2s_met_dtw(p(xp), p(xo_d), tx, mx, p(yp), p(yo_d), ty, my, B, dim, r, flags, p(out["cost"]), p(out["mse"]),
+                          p(out["path_len"]), p(out["status"]), p(path), p(po_d), p(ws), nbytes,
+                          torch.cuda.current_stream(device).cuda_stream))
+    return out
 
 
 def _run(x, x_lengths, y, y_lengths, radius, flags, return_paths):
-    lib = load()
-    device = x.device if isinstance(x, torch.Tensor) and x.is_cuda else _device()
-    xt, yt = _as_batch(x, device, "x"), _as_batch(y, device, "y")
+    device = ragged.device("the DTW metric", x)
+    xt, yt = ragged.as_batch(x, device, "x"), ragged.as_batch(y, device, "y")
     B = int(xt.shape[0])
     if int(yt.shape[0]) != B:
         raise B2SError("x has %d pairs, y has %d" % (B, int(yt.shape[0])))
     dim = int(xt.shape[2])
     if int(yt.shape[2]) != dim:
         raise B2SError("x has %d features, y has %d" % (dim, int(yt.shape[2])))
-    lx = _lengths(x_lengths, B, int(xt.shape[1]), "x_lengths")
-    ly = _lengths(y_lengths, B, int(yt.shape[1]), "y_lengths")
-    r = _c_radius(radius)
-    xp, xo = _pack(xt, lx)
-    yp, yo = _pack(yt, ly)
-    tx, ty, mx, my = int(xo[-1]), int(yo[-1]), max(lx), max(ly)
-    nbytes = lib.b2s_met_dtw_ws_bytes(B, tx, ty, mx, my, dim, r, flags)
-    if nbytes == 0:
-        check(1)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    xo_d = torch.from_numpy(xo).to(device)
-    yo_d = torch.from_numpy(yo).to(device)
-    cost = torch.empty(B, dtype=torch.float64, device=device)
-    mse = torch.empty(B, dtype=torch.float64, device=device)
-    plen = torch.empty(B, dtype=torch.int32, device=device)
-    status = torch.empty(B, dtype=torch.int32, device=device)
-    path = po_d = None
-    if return_paths:
-        po = np.zeros(B + 1, dtype=np.int32)
-        np.cumsum([a + b for a, b in zip(lx, ly)], out=po[1:])
-        path = torch.empty(max(1, int(po[-1])), 2, dtype=torch.int32, device=device)
-        po_d = torch.from_numpy(po).to(device)
-
-    def p(t):
-        return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
-    stream = torch.cuda.current_stream(device).cuda_stream
-    check(lib.b2s_met_dtw(p(xp), p(xo_d), tx, mx, p(yp), p(yo_d), ty, my, B, dim, r, flags, p(cost), p(mse), p(plen), p(status),
-                          p(path), p(po_d), p(ws), nbytes, stream))
-    out = {"cost": cost, "mse": mse, "path_len": plen, "status": status}
-    if return_paths:
-        out["path"], out["path_offsets"] = path, po
-    return out
-
-
-def _paths(out):
-    """Host copies of the paths: list of int64 [L_b, 2] arrays (empty for EMPTY / FAILED pairs)."""
-    path = out["path"].cpu().numpy()
-    plen = out["path_len"].cpu().numpy()
-    po = out["path_offsets"]
-    return [path[po[b]:po[b] + plen[b]].astype(np.int64) for b in range(len(plen))]
+    lx = ragged.lengths(x_lengths, B, int(xt.shape[1]), "x_lengths")
+    ly = ragged.lengths(y_lengths, B, int(yt.shape[1]), "y_lengths")
+    r = c_radius(radius)
+    xp, xo = ragged.pack(xt, lx)
+    yp, yo = ragged.pack(yt, ly)
+    po = ragged.offsets([a + b for a, b in zip(lx, ly)]) if return_paths else None
+    return dtw_packed(xp, torch.from_numpy(xo).to(device), int(xo[-1]), max(lx), yp, torch.from_numpy(yo).to(device), int(yo[-1]),
+                      max(ly), B, dim, r, flags, po)
 
 
 def _raise_failed(status):
@@ -177,7 +106,7 @@ def dtw_batch(x, x_lengths, y, y_lengths, radius=1, return_paths=False):
     out = _run(x, x_lengths, y, y_lengths, radius, 0, return_paths)
     _raise_failed(out["status"])
     cost = torch.where(out["status"] == OK, out["cost"], torch.full_like(out["cost"], float("nan")))
-    return (cost, _paths(out)) if return_paths else cost
+    return (cost, ragged.paths(out)) if return_paths else cost
 
 
 def fastdtw(x, y, radius=1):
@@ -219,20 +148,7 @@ _ORIGINAL = "_b2s_reference_calculate_mse_dtw"
 def install(hp=None):
     """Bind utils.infolog.calculate_mse_dtw (the reference's module, if imported) to this module's function for hp.mse_dtw == "hip";
     restore the original for "reference".  Anything else is a ValueError."""
-    if hp is None:
-        from hyperparams import hparams as hp
-    mode = hp.mse_dtw
-    if mode not in MSE_DTW_CHOICES:
-        raise ValueError("unknown mse_dtw %r (expected 'reference' or 'hip')" % (mode,))
-    mod = sys.modules.get("utils.infolog")
-    if mod is None or not hasattr(mod, "calculate_mse_dtw"):
-        return
-    bound = mod.calculate_mse_dtw is calculate_mse_dtw
-    if mode == "hip" and not bound:
-        setattr(mod, _ORIGINAL, mod.calculate_mse_dtw)
-        mod.calculate_mse_dtw = calculate_mse_dtw
-        logging.info("mse_dtw=hip: utils.infolog.calculate_mse_dtw now runs on the GPU (b2s_hip.metrics)")
-    elif mode == "reference" and bound and hasattr(mod, _ORIGINAL):
-        mod.calculate_mse_dtw = getattr(mod, _ORIGINAL)
-        delattr(mod, _ORIGINAL)
-        logging.info("mse_dtw=reference: utils.infolog.calculate_mse_dtw restored")
+    on = choice(hp, "mse_dtw") == "hip"
+    if rebind("utils.infolog", "calculate_mse_dtw", calculate_mse_dtw, _ORIGINAL, on):
+        logging.info("mse_dtw=hip: utils.infolog.calculate_mse_dtw now runs on the GPU (b2s_hip.metrics)" if on else
+                     "mse_dtw=reference: utils.infolog.calculate_mse_dtw restored")

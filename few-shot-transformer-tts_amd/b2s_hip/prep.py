@@ -64,13 +64,6 @@ def _device_batch(wavs, lengths):
     return wavs, B, Lmax, torch.tensor(samples, dtype=torch.int32).to(wavs.device)
 
 
-def _workspace(lib, B, Lmax, which, device):
-    nbytes = lib.b2s_voc_prep_ws_bytes(B, Lmax, which)
-    if nbytes == 0:
-        vocoder.check(1)
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
-
-
 def _trim_device(wavs, lengths, gap_threshold):
     """One b2s_voc_prep_trim call, nothing synchronised: (out [B, Lmax + 4000] cuda fp32, meta [4, B] cuda int32 holding out_lengths,
     status, n_removed and the bit patterns of v95)."""
@@ -79,7 +72,7 @@ def _trim_device(wavs, lengths, gap_threshold):
         raise B2SError("gap_threshold must be an integer number of samples, got %r" % (gap_threshold,))
     wavs, B, Lmax, lens = _device_batch(wavs, lengths)
     device = wavs.device
-    ws = _workspace(lib, B, Lmax, WS_TRIM, device)
+    ws = vocoder.workspace(lib.b2s_voc_prep_ws_bytes(B, Lmax, WS_TRIM), device)
     out = torch.empty(B, Lmax + LEAD + TAIL, dtype=torch.float32, device=device)
     meta = torch.empty(4, B, dtype=torch.int32, device=device)
     vocoder.check(lib.b2s_voc_prep_trim(ptr(wavs), ptr(lens), B, Lmax, int(gap_threshold), ptr(out), ptr(meta[0]), ptr(meta[1]),
@@ -143,13 +136,10 @@ def _resample_device(wavs, lengths, orig_sr):
     if any(n < 1 or n > Lmax for n in samples):
         raise B2SError("every length must be in 1..Lmax=%d samples (got %s)" % (Lmax, samples))
     device = wavs.device
-    nbytes = lib.b2s_voc_resample_ws_bytes(B, Lmax, channels, int(orig_sr))
-    if nbytes == 0:
-        vocoder.check(1)
+    ws = vocoder.workspace(lib.b2s_voc_resample_ws_bytes(B, Lmax, channels, int(orig_sr)), device)
     counts = np.array([resample_lengths(n, int(orig_sr)) for n in samples], dtype=np.int32).reshape(B, 2)
     Lmax_out = max(1, int(counts[:, 1].max()))
     meta = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.array(samples, np.int32)[:, None], counts], axis=1).T)).to(device)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
     out = torch.empty(B, Lmax_out, dtype=torch.float32, device=device)
     vocoder.check(lib.b2s_voc_resample(ptr(wavs), ptr(meta[0]), B, Lmax, channels, int(orig_sr), ptr(meta[1]), ptr(meta[2]), Lmax_out,
                                        ptr(out), ptr(ws), ws.numel(), torch.cuda.current_stream(device).cuda_stream))
@@ -182,7 +172,7 @@ def abs_quantile_batch(wavs, lengths, intervals, fraction=0.95):
     device = wavs.device
     iv_dev = torch.from_numpy(pad).to(device)
     n_dev = torch.tensor([len(iv) for iv in ivs], dtype=torch.int32).to(device)
-    ws = _workspace(lib, B, Lmax, WS_QUANTILE, device)
+    ws = vocoder.workspace(lib.b2s_voc_prep_ws_bytes(B, Lmax, WS_QUANTILE), device)
     out = torch.empty(B, dtype=torch.float32, device=device)
     vocoder.check(lib.b2s_voc_prep_abs_quantile(ptr(wavs), ptr(lens), B, Lmax, ptr(iv_dev), ptr(n_dev), NI, float(fraction), ptr(out),
                                                 ptr(ws), ws.numel(), torch.cuda.current_stream(device).cuda_stream))

@@ -8,16 +8,14 @@ values are refused by the library with a message naming the supported set.  The 
 1 <= hop_length <= frame_length.
 """
 import ctypes as C
-import os
 import wave
 
 import numpy as np
 import torch
 
+from . import ragged
+from .cbind import Library
 from .lib import B2SError, ptr
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(os.path.dirname(_HERE), "libb2s_vocoder.so")
 
 WS_MEL2WAV, WS_WAV2MEL = 0, 1
 
@@ -46,31 +44,8 @@ _PROTOS = {
     "b2s_voc_resample_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "b2s_voc_resample": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, C.c_int, P, P, C.c_size_t, P]),
 }
-EXPORTS = sorted(_PROTOS)
-
-_lib = None
-
-
-def load():
-    """Load libb2s_vocoder.so (raises B2SError if it is missing -- there is no fallback path)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise B2SError("libb2s_vocoder.so not found at %s -- build it with few-shot-transformer-tts_amd/csrc/build.sh "
-                       "(or __graft_entry__.build()); there is no CPU fallback" % LIB_PATH)
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in _PROTOS.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
-    return lib
-
-
-def check(rc):
-    if rc != 0:
-        raise B2SError(load().b2s_voc_last_error().decode("utf-8", "replace"))
+_LIB = Library("libb2s_vocoder.so", _PROTOS, "b2s_voc_last_error")
+LIB_PATH, EXPORTS, load, check, workspace = _LIB.path, _LIB.exports, _LIB.load, _LIB.check, _LIB.workspace
 
 
 def _hp(hp=None):
@@ -144,19 +119,6 @@ def _device_tables(hp, device):
 
 # ------------------------------------------------------------------------------------------------------------------- batched calls
 
-def _offsets(frames, device):
-    off = np.zeros(len(frames) + 1, dtype=np.int32)
-    np.cumsum(frames, out=off[1:])
-    return off, torch.from_numpy(off).to(device)
-
-
-def _workspace(lib, prm, B, total, max_frames, which, device):
-    nbytes = lib.b2s_voc_ws_bytes(C.byref(prm), B, total, max_frames, which)
-    if nbytes == 0:
-        check(1)
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
-
-
 def mel2wav_batch(mels, lengths, n_iter=None, hp=None):
     """Vocode a padded batch of normalised mels [B, Tmax, n_mels] (cuda tensor or NumPy) with per-utterance frame counts `lengths`
     (host sequence, every T_b >= 2).  Returns (wav [B, hop * (Tmax - 1)] cuda fp32, zero past each hop * (T_b - 1), wav_lengths).
@@ -179,9 +141,9 @@ def mel2wav_batch(mels, lengths, n_iter=None, hp=None):
         raise B2SError("every length must be in 2..Tmax=%d (got %s); T = 1 gives an empty waveform" % (Tmax, frames))
     prm = params(hp)
     device = mels.device
-    off_h, off = _offsets(frames, device)
+    off_h, off = ragged.offsets(frames, device)
     total = int(off_h[-1])
-    ws = _workspace(lib, prm, B, total, Tmax, WS_MEL2WAV, device)
+    ws = workspace(lib.b2s_voc_ws_bytes(C.byref(prm), B, total, Tmax, WS_MEL2WAV), device)
     _, inv_t = _device_tables(hp, device)
     wav = torch.empty(B, int(hp.hop_length) * (Tmax - 1), dtype=torch.float32, device=device)
     check(lib.b2s_voc_mel2wav(C.byref(prm), ptr(mels), ptr(off), B, Tmax, total, n_iter, ptr(inv_t), ptr(wav), ptr(ws),
@@ -212,10 +174,10 @@ def wav2mel_batch(wavs, lengths, hp=None):
     hop = int(hp.hop_length)
     device = wavs.device
     frames = [1 + n // hop for n in samples]
-    off_h, off = _offsets(frames, device)
+    off_h, off = ragged.offsets(frames, device)
     total = int(off_h[-1])
     Tout = 1 + Lmax // hop
-    ws = _workspace(lib, prm, B, total, Tout, WS_WAV2MEL, device)
+    ws = workspace(lib.b2s_voc_ws_bytes(C.byref(prm), B, total, Tout, WS_WAV2MEL), device)
     basis, _ = _device_tables(hp, device)
     lens = torch.tensor(samples, dtype=torch.int32).to(device)
     mels = torch.zeros(B, Tout, int(hp.num_mels), dtype=torch.float32, device=device)
@@ -251,13 +213,10 @@ def _split_device(wavs, lengths, top_db, frame_length, hop_length, want_flags=Fa
         raise B2SError("every length must be in 2..Lmax=%d samples (got %s)" % (Lmax, samples))
     top_db, fl, hop = float(top_db), int(frame_length), int(hop_length)
     device = wavs.device
-    nbytes = lib.b2s_voc_silence_ws_bytes(B, Lmax, fl, hop)
-    if nbytes == 0:
-        check(1)
+    ws = workspace(lib.b2s_voc_silence_ws_bytes(B, Lmax, fl, hop), device)
     frames = [1 + (n + 2 * (fl // 2) - fl) // hop for n in samples]
     fmax = 1 + (Lmax + 2 * (fl // 2) - fl) // hop
     ni = (fmax + 1) // 2
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
     lens = torch.tensor(samples, dtype=torch.int32).to(device)
     i32 = dict(dtype=torch.int32, device=device)
     out = {"intervals": torch.empty(B, ni, 2, **i32), "n": torch.empty(B, **i32), "trim": torch.empty(B, 2, **i32),

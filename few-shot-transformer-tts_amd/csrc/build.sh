@@ -24,24 +24,25 @@ for p in "${pids[@]}"; do wait $p; done
 objs=""; for f in $SRCS; do objs="$objs $OBJ/$f.o"; done
 hipcc --offload-arch=gfx950 -shared -fPIC $objs -o $OUT
 echo "built $OUT"
-# the vocoder / mel front end is a library of its own (include/b2s_vocoder.h); not part of the measurement build
+# A satellite library: ../libb2s_NAME.so from its sources plus the shared error core (side_common.hip), rebuilt when any of them,
+# side_common.h or its header include/b2s_NAME.h is newer.  satellite NAME "EXTRA FLAGS" SOURCE...
+MODE=$1
+satellite() {
+  local out=../libb2s_$1.so header=../../include/b2s_$1.h extra=$2 stale=$MODE f
+  shift 2
+  local srcs="$* side_common.hip"
+  for f in $srcs side_common.h $header; do
+    if [ ! -f $out ] || [ $f -nt $out ]; then stale=--clean; fi
+  done
+  if [ "$stale" = "--clean" ]; then hipcc $FLAGS $extra -shared $srcs -o $out; fi
+  echo "built $out"
+}
+# not part of the measurement build
 if [ "$1" != "--lab" ]; then
-  VOUT=../libb2s_vocoder.so
-  if [ "$1" = "--clean" ] || [ ! -f $VOUT ] || [ vocoder/vocoder.hip -nt $VOUT ] || [ vocoder/silence.hip -nt $VOUT ] || [ vocoder/prep.hip -nt $VOUT ] || [ vocoder/resample.hip -nt $VOUT ] || [ ../../include/b2s_vocoder.h -nt $VOUT ]; then
-    hipcc $FLAGS -shared vocoder/vocoder.hip vocoder/silence.hip vocoder/prep.hip vocoder/resample.hip -o $VOUT
-  fi
-  echo "built $VOUT"
-  # batched FastDTW / MSE-after-DTW eval metric, alignment-head selection and edit distance: a library of its own too (include/b2s_metrics.h)
-  MOUT=../libb2s_metrics.so
-  if [ "$1" = "--clean" ] || [ ! -f $MOUT ] || [ metrics/dtw.hip -nt $MOUT ] || [ metrics/align.hip -nt $MOUT ] || [ metrics/edit.hip -nt $MOUT ] || [ metrics/met_common.h -nt $MOUT ] || [ ../../include/b2s_metrics.h -nt $MOUT ]; then
-    hipcc $FLAGS -shared metrics/dtw.hip metrics/align.hip metrics/edit.hip -o $MOUT
-  fi
-  echo "built $MOUT"
-  # mel-cepstral distortion after DTW: the cepstral front end and the scoring along the path (include/b2s_mcd.h); contraction off,
-  # the definition rounds every product and sum on its own
-  COUT=../libb2s_mcd.so
-  if [ "$1" = "--clean" ] || [ ! -f $COUT ] || [ mcd/mcd.hip -nt $COUT ] || [ ../../include/b2s_mcd.h -nt $COUT ]; then
-    hipcc $FLAGS -ffp-contract=off -shared mcd/mcd.hip -o $COUT
-  fi
-  echo "built $COUT"
+  # the vocoder / mel front end, silence trimming, corpus preparation and resampling (include/b2s_vocoder.h)
+  satellite vocoder "" vocoder/vocoder.hip vocoder/silence.hip vocoder/prep.hip vocoder/resample.hip
+  # batched FastDTW / MSE-after-DTW eval metric, alignment-head selection and edit distance (include/b2s_metrics.h)
+  satellite metrics "" metrics/dtw.hip metrics/align.hip metrics/edit.hip
+  # mel-cepstral distortion after DTW (include/b2s_mcd.h); contraction off, the definition rounds every product and sum on its own
+  satellite mcd "-ffp-contract=off" mcd/mcd.hip
 fi

@@ -15,10 +15,11 @@
 // per-thread sum in step order and a fixed tree over the threads.  Integer ballots only, no atomics.
 #include <hip/hip_runtime.h>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <string>
 #include "../../../include/b2s_mcd.h"
+#include "../side_common.h"
+
+using b2s_side::align_up;
+using b2s_side::fail;
 
 #pragma clang fp contract(off)
 
@@ -29,20 +30,6 @@ constexpr int CHUNK = 64;             // frames per workgroup: one ballot ranks 
 constexpr int FB_MAX = 16;            // voiced frames whose log-magnitudes are in LDS at once
 constexpr int LN_BYTES = 16 * 1024;   // LDS for them
 constexpr int TAB_BYTES = 32 * 1024;  // LDS for the DCT rows
-
-thread_local std::string g_err;
-
-__attribute__((format(printf, 1, 2))) int fail(const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return 1;
-}
-
-inline size_t align_up(size_t v) { return (v + 255) & ~size_t(255); }
 
 inline int chunks_of(int max_len) { return max_len > 0 ? (max_len + CHUNK - 1) / CHUNK : 1; }
 
@@ -286,7 +273,7 @@ extern "C" {
 
 int b2s_mcd_version(void) { return 100; }
 
-const char *b2s_mcd_last_error(void) { return g_err.c_str(); }
+const char *b2s_mcd_last_error(void) { return b2s_side::last_error(); }
 
 size_t b2s_mcd_ws_bytes(int B, int max_len) {
     if (check_ws_args(B, max_len)) return 0;
@@ -323,9 +310,7 @@ int b2s_mcd_cepstra(const float *mel, const int32_t *offsets, int total, int max
                        status_out);
     hipLaunchKernelGGL(k_mcd_cepstra, dim3(B * S), dim3(NT), (FB + KC) * row_bytes, s, mel, offsets, total, max_len, n_mels, order, S,
                        dct, sc, FB, KC, bases, cep_out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("cepstra: launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return b2s_side::launch_status("cepstra");
 }
 
 int b2s_mcd_score(const float *cx, const int32_t *cx_offsets, int total_cx, const float *cy, const int32_t *cy_offsets, int total_cy,
@@ -341,9 +326,7 @@ int b2s_mcd_score(const float *cx, const int32_t *cx_offsets, int total_cx, cons
     if (!mcd_out || !status_out) return fail("score: mcd_out or status_out is NULL");
     hipLaunchKernelGGL(k_mcd_score, dim3(B), dim3(NT), 0, (hipStream_t)stream, cx, cx_offsets, total_cx, cy, cy_offsets, total_cy, order,
                        path, path_offsets, total_path, path_len, dtw_status, db_scale, mcd_out, status_out, dist_out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("score: launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return b2s_side::launch_status("score");
 }
 
 }  // extern "C"

@@ -22,11 +22,11 @@
 #include <cmath>
 #include <cstdint>
 #include "../../../include/b2s_metrics.h"
-#include "met_common.h"
+#include "../side_common.h"
 
 namespace {
 
-using b2s_met::fail;
+using b2s_side::fail;
 
 constexpr int NT = 256;               // threads per block
 constexpr int CHUNK = 256;            // frames per workgroup: 64 lanes x 4 frames
@@ -305,9 +305,7 @@ int b2s_met_align_select(const float *const *layers, int n_layers, int B, int H,
     hipLaunchKernelGGL(k_met_align_finish, dim3(B, map_out ? FIN_SPLIT : 1), dim3(NT), 0, (hipStream_t)stream, lp, LH, H, S, T,
                        l.n_chunks, enc_len, dec_len, (const double *)(w + l.part), (const int32_t *)(w + l.amax),
                        (uint32_t *)(w + l.visited), scores_out, best_out, map_out, path_out, stats_out, vec_map);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("align: launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return b2s_side::launch_status("align");
 }
 
 }  // extern "C"

@@ -16,11 +16,11 @@
 // workspace; a single lane backtracks.  Expect the kernel to be latency-bound: the DP is a chain of ~nx + ny steps per level.
 #include <hip/hip_runtime.h>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <string>
 #include "../../../include/b2s_metrics.h"
-#include "met_common.h"
+#include "../side_common.h"
+
+using b2s_side::align_up;
+using b2s_side::fail;
 
 namespace {
 
@@ -30,9 +30,6 @@ constexpr int GRP = 16;               // lanes per distance (feature dimension s
 constexpr int MAX_DIM = 256;
 constexpr int MAX_LEVELS = 40;
 constexpr int LDS_BYTES = 64 * 1024 - 1024;    // dynamic LDS per block (the static level table and scalars take the rest of 64 KiB)
-
-thread_local std::string g_err;
-using b2s_met::fail;
 
 // LDS plan, sized by the longest sequences: distance tiles, the strip boundary row, per-row window / offsets, the coarse path's
 // row extents, then back-pointers in whatever is left.
@@ -54,8 +51,6 @@ __host__ __device__ inline LdsPlan lds_plan(int max_x, int max_y) {
     p.bp_cap = LDS_BYTES - p.bp;
     return p;
 }
-
-inline size_t align_up(size_t v) { return (v + 255) & ~size_t(255); }
 
 // back-pointer bytes per pair in the workspace: the exact mode's full matrix, or a bound on a fastdtw level's window
 // (rows: 2 (pmax - pmin) + 4r + 2 columns each, summed: (nx + 2)(8r + 2) + (4r + 2) ny; the coarsest level: (r + 1) max(nx, ny))
@@ -380,22 +375,11 @@ __global__ __launch_bounds__(NT) void k_met_dtw(const float *__restrict__ x, con
 
 }  // namespace
 
-// the library's one error slot (met_common.h): every source of libb2s_metrics.so reports through it
-int b2s_met::fail(const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return 1;
-}
-
 extern "C" {
 
 int b2s_met_version(void) { return 100; }
 
-const char *b2s_met_last_error(void) { return g_err.c_str(); }
+const char *b2s_met_last_error(void) { return b2s_side::last_error(); }
 
 size_t b2s_met_dtw_ws_bytes(int B, int total_x, int total_y, int max_x, int max_y, int dim, int radius, int flags) {
     if (check_args(B, total_x, total_y, max_x, max_y, dim, radius, flags)) return 0;
@@ -418,9 +402,7 @@ int b2s_met_dtw(const float *x, const int32_t *x_offsets, int total_x, int max_x
                        total_y, max_y, dim, radius, flags & B2S_MET_VOICED_ONLY, cost_out, mse_out, path_len_out, status_out,
                        path_out, path_offsets, (double *)(w + l.px), (double *)(w + l.py), (int32_t *)(w + l.path),
                        (uint8_t *)(w + l.bp), l.bp_stride);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("dtw: launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return b2s_side::launch_status("dtw");
 }
 
 }  // extern "C"

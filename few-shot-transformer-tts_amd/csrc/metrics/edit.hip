@@ -22,11 +22,11 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../../../include/b2s_metrics.h"
-#include "met_common.h"
+#include "../side_common.h"
 
 namespace {
 
-using b2s_met::fail;
+using b2s_side::fail;
 
 constexpr int MAX_LEN = 4096;         // symbols per side: 64 lanes x 64 columns
 constexpr int NT = 256;               // threads per block = 4 pairs
@@ -175,9 +175,7 @@ int b2s_met_edit_distance(const int32_t *a, const int32_t *a_offsets, int total_
     else if (need <= 32) B2S_EDIT_LAUNCH(32);
     else B2S_EDIT_LAUNCH(64);
 #undef B2S_EDIT_LAUNCH
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("edit: launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return b2s_side::launch_status("edit");
 }
 
 }  // extern "C"

@@ -19,11 +19,11 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../../../include/b2s_vocoder.h"
+#include "../side_common.h"
 
-namespace b2s_voc {
-int fail(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-}
-using b2s_voc::fail;
+using b2s_side::align_up;
+using b2s_side::fail;
+using b2s_side::launch_status;
 
 namespace {
 
@@ -357,8 +357,6 @@ __global__ __launch_bounds__(NT) void k_prep_margins(const float *__restrict__ y
     }
 }
 
-constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 int check_shape(const char *what, int B, int Lmax) {
     if (B <= 0) return fail("%s: B must be > 0 (got %d)", what, B);
     if (B > 65535) return fail("%s: B must be <= 65535 (got %d)", what, B);
@@ -376,7 +374,7 @@ struct Layout {
 Layout layout(int B, int Lmax) {
     Layout l;
     size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += align256(bytes); return o; };
+    auto take = [&](size_t bytes) { const size_t o = at; at += align_up(bytes); return o; };
     const size_t i32 = sizeof(int32_t);
     l.NI1 = max_intervals(Lmax, FL1, HOP1);
     l.NI2 = max_intervals(Lmax, FL2, HOP2);
@@ -404,12 +402,6 @@ Layout layout(int B, int Lmax) {
     l.ol2 = take(i32 * B);
     l.total = at;
     return l;
-}
-
-int launch_status(const char *what) {
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail("%s: launch failed: %s", what, hipGetErrorString(err));
-    return 0;
 }
 
 // the three histogram / scan passes; hist must be zero on entry and is zero again on exit

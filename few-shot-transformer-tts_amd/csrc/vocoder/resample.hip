@@ -26,11 +26,10 @@
 #include <cmath>
 #include <cstdint>
 #include "../../../include/b2s_vocoder.h"
+#include "../side_common.h"
 
-namespace b2s_voc {
-int fail(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-}
-using b2s_voc::fail;
+using b2s_side::fail;
+using b2s_side::launch_status;
 
 namespace {
 
@@ -219,12 +218,6 @@ Layout layout(int B, int Lmax_in, int channels) {
     l.mono = sizeof(float) * (size_t)TABLE_PAD;                          // a multiple of 256 bytes
     l.total = l.mono + (channels > 1 ? sizeof(float) * (size_t)B * Lmax_in : 0);
     return l;
-}
-
-int launch_status(const char *what) {
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail("%s: launch failed: %s", what, hipGetErrorString(err));
-    return 0;
 }
 
 }  // namespace

@@ -14,11 +14,11 @@
 #include <cmath>
 #include <cstdint>
 #include "../../../include/b2s_vocoder.h"
+#include "../side_common.h"
 
-namespace b2s_voc {
-int fail(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-}
-using b2s_voc::fail;
+using b2s_side::align_up;
+using b2s_side::fail;
+using b2s_side::launch_status;
 
 namespace {
 
@@ -225,14 +225,6 @@ int check_shape(const char *what, int B, int Lmax, int fl, int hop) {
     return 0;
 }
 
-constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-int launch_status(const char *what) {
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail("%s: launch failed: %s", what, hipGetErrorString(err));
-    return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -240,7 +232,7 @@ extern "C" {
 size_t b2s_voc_silence_ws_bytes(int B, int Lmax, int frame_length, int hop_length) {
     if (check_shape("silence_ws_bytes", B, Lmax, frame_length, hop_length)) return 0;
     const int Fmax = n_frames(Lmax, frame_length, hop_length);
-    return align256(sizeof(float) * (size_t)B * Fmax) + align256(sizeof(unsigned int) * (size_t)B);
+    return align_up(sizeof(float) * (size_t)B * Fmax) + align_up(sizeof(unsigned int) * (size_t)B);
 }
 
 int b2s_voc_silence_split(const float *wav, const int32_t *lengths, int B, int Lmax, double top_db, int frame_length, int hop_length,
@@ -256,7 +248,7 @@ int b2s_voc_silence_split(const float *wav, const int32_t *lengths, int B, int L
     const int tile = tile_frames(frame_length, hop_length);
     hipStream_t st = (hipStream_t)stream;
     float *mse = (float *)ws;
-    unsigned int *maxbits = (unsigned int *)((char *)ws + align256(sizeof(float) * (size_t)B * Fmax));
+    unsigned int *maxbits = (unsigned int *)((char *)ws + align_up(sizeof(float) * (size_t)B * Fmax));
     const hipError_t me = hipMemsetAsync(maxbits, 0, sizeof(unsigned int) * (size_t)B, st);
     if (me != hipSuccess) return fail("silence_split: clearing the maxima failed: %s", hipGetErrorString(me));
     hipLaunchKernelGGL(k_sil_energy, dim3((Fmax + tile - 1) / tile, B), dim3(NT), 0, st, wav, lengths, Lmax, frame_length, hop_length, tile,

@@ -11,11 +11,13 @@
 // frame's new windowed segment.  A gather: no atomics, deterministic, and a frame's result does not depend on its batch.
 #include <hip/hip_runtime.h>
 #include <cfloat>
-#include <cstdarg>
 #include <cmath>
-#include <cstdio>
-#include <string>
 #include "../../../include/b2s_vocoder.h"
+#include "../side_common.h"
+
+using b2s_side::align_up;
+using b2s_side::fail;
+using b2s_side::launch_status;
 
 namespace {
 
@@ -26,27 +28,6 @@ constexpr int HALF = WIN / 2;         // a frame covers y[t * HOP - HALF, t * HO
 constexpr int MAX_LOOKBACK = 1024;    // de-emphasis look-back bound (samples)
 constexpr int OLA_CHUNK = 32, OLA_SPAN = NT * OLA_CHUNK;
 constexpr int MAG_FRAMES = 16;        // frames per block of k_voc_mag (one read of the inverse basis serves all of them)
-
-thread_local std::string g_err;
-
-}  // namespace
-
-// shared with silence.hip (same library): sets the message b2s_voc_last_error() returns, and returns 1
-namespace b2s_voc {
-int fail(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-int fail(const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return 1;
-}
-}  // namespace b2s_voc
-using b2s_voc::fail;
-
-namespace {
 
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 __device__ __forceinline__ float2 cconj(float2 a) { return make_float2(a.x, -a.y); }
@@ -353,8 +334,6 @@ __global__ __launch_bounds__(NT) void k_voc_wav2mel(const float *__restrict__ wa
     }
 }
 
-constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct WsLayout {
     size_t tw, win, bands, S, seg0, seg1, total;
 };
@@ -362,14 +341,14 @@ struct WsLayout {
 WsLayout layout(int which, int F) {
     WsLayout l{};
     size_t o = 0;
-    l.tw = o; o += align256(sizeof(float2) * NTW);
-    l.win = o; o += align256(sizeof(float) * WIN);
+    l.tw = o; o += align_up(sizeof(float2) * NTW);
+    l.win = o; o += align_up(sizeof(float) * WIN);
     if (which == B2S_VOC_WS_MEL2WAV) {
-        l.S = o; o += align256(sizeof(float) * (size_t)F * NBIN);
-        l.seg0 = o; o += align256(sizeof(float) * (size_t)F * WIN);
-        l.seg1 = o; o += align256(sizeof(float) * (size_t)F * WIN);
+        l.S = o; o += align_up(sizeof(float) * (size_t)F * NBIN);
+        l.seg0 = o; o += align_up(sizeof(float) * (size_t)F * WIN);
+        l.seg1 = o; o += align_up(sizeof(float) * (size_t)F * WIN);
     } else {
-        l.bands = o; o += align256(sizeof(int2) * NMEL);
+        l.bands = o; o += align_up(sizeof(int2) * NMEL);
     }
     l.total = o;
     return l;
@@ -401,12 +380,6 @@ int check_counts(int B, int frames_per_utt_max, int total_frames, int min_frames
     return 0;
 }
 
-int launch_status(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("%s: launch failed: %s", what, hipGetErrorString(e));
-    return 0;
-}
-
 int gl_grid(int F) { return F < 256 * 5 ? F : 256 * 5; }      // persistent: 5 blocks of 256 threads per CU fit the LDS
 
 }  // namespace
@@ -415,7 +388,7 @@ extern "C" {
 
 int b2s_voc_version(void) { return 100; }
 
-const char *b2s_voc_last_error(void) { return g_err.c_str(); }
+const char *b2s_voc_last_error(void) { return b2s_side::last_error(); }
 
 size_t b2s_voc_ws_bytes(const B2SVocParams *p, int B, int total_frames, int max_frames, int which) {
     if (check_params(p)) return 0;

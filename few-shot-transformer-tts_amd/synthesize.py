@@ -24,6 +24,7 @@ import torch
 
 from hyperparams import hparams as hp
 from b2s_hip import lib as L
+from b2s_hip.cbind import choice
 from b2s_hip.engine import _i32
 
 
@@ -292,9 +293,7 @@ def save_eval_results(names, mel_pre, mel_aft, alignments, input_lengths, genera
         import json
         from b2s_hip import alignment
         can_plot = importlib.util.find_spec("matplotlib") is not None      # decided once; the diagnostics are written either way
-    if hp.trim not in ("reference", "hip"):
-        raise ValueError("unknown trim %r (expected 'reference' or 'hip')" % (hp.trim,))
-    if hp.trim == "hip" and hp.vocoder == "reference":
+    if choice(hp, "trim") == "hip" and hp.vocoder == "reference":
         raise ValueError("trim=hip needs vocoder=hip: it trims the GPU vocoder's waveforms on the device")
     os.makedirs(output_dir, exist_ok=True)
     gpu_wavs = gpu_trimmed = None

@@ -179,17 +179,17 @@ def test_argument_errors_come_back_as_messages_without_a_gpu():
 
 
 def test_python_wrappers_refuse_bad_arguments_before_the_gpu():
-    from b2s_hip import B2SError, metrics
+    from b2s_hip import B2SError, metrics, ragged
     x = np.zeros((2, 5, 3), np.float32)
     with pytest.raises(B2SError, match="radius must be >= 1"):
-        metrics._c_radius(0)
-    assert metrics._c_radius(None) == -1 and metrics._c_radius(2) == 2
+        metrics.c_radius(0)
+    assert metrics.c_radius(None) == -1 and metrics.c_radius(2) == 2
     with pytest.raises(B2SError, match="must be >= 0"):
-        metrics._lengths([3, -1], 2, 5, "x_lengths")
+        ragged.lengths([3, -1], 2, 5, "x_lengths")
     with pytest.raises(B2SError, match="3 x_lengths for a batch of 2"):
-        metrics._lengths([3, 1, 2], 2, 5, "x_lengths")
-    assert metrics._lengths(np.array([7, 2]), 2, 5, "x") == [5, 2]            # sliced past the end, like x[i, :n]
-    packed, off = metrics._pack(metrics._as_batch(x + np.arange(5)[None, :, None], "cpu", "x"), [3, 2])
+        ragged.lengths([3, 1, 2], 2, 5, "x_lengths")
+    assert ragged.lengths(np.array([7, 2]), 2, 5, "x") == [5, 2]              # sliced past the end, like x[i, :n]
+    packed, off = ragged.pack(ragged.as_batch(x + np.arange(5)[None, :, None], "cpu", "x"), [3, 2])
     assert packed.shape == (5, 3) and off.tolist() == [0, 3, 5] and packed[:, 0].tolist() == [0, 1, 2, 0, 1]
 
 

@@ -199,7 +199,8 @@ def test_inconsistent_offsets_fail_that_utterance_only(monkeypatch):
     cfg = CONFIGS[0]
     preds, targets, hp, ref, got = case(cfg)
     t = torch.from_numpy(preds).cuda()
-    rows, off = mcd._pack(t, LX)
+    pack = mcd.ragged.pack
+    rows, off = pack(t, LX)
     bad = off.copy()
     bad[-1] += 3                                             # the last utterance runs 3 rows past the buffer
     out = mcd.cepstra_packed(rows, torch.from_numpy(bad).cuda(), max(LX) + 3, cfg[1], hp)
@@ -215,11 +216,11 @@ def test_inconsistent_offsets_fail_that_utterance_only(monkeypatch):
         assert [b for b, s in enumerate(st) if s == mcd.FAILED] == failed
 
     def bad_pack(t, lengths):
-        rows, off = mcd.metrics._pack(t, lengths)
+        rows, off = pack(t, lengths)
         off = off.copy()
         off[-1] += 3
         return rows, off
-    monkeypatch.setattr(mcd, "_pack", bad_pack)
+    monkeypatch.setattr(mcd.ragged, "pack", bad_pack)
     with pytest.raises(mcd.B2SError, match=r"failed for utterances \[6\]"):
         mcd.mcd_dtw_batch(preds, LX, targets, LY, hp=hp)
     res = mcd.mcd_dtw_details(preds, LX, targets, LY, hp=hp)
