@@ -1,5 +1,5 @@
 #!/bin/bash
-# Build libb2s_hip.so, libb2s_vocoder.so, libb2s_metrics.so and libb2s_mcd.so for gfx950 (MI355X).  hipcc cross-compiles without a GPU.
+# Build libb2s_hip.so, libb2s_vocoder.so, libb2s_metrics.so, libb2s_mcd.so and libb2s_f0.so for gfx950 (MI355X).  hipcc cross-compiles without a GPU.
 #   build.sh            only what changed
 #   build.sh --clean    recompile every source (what __graft_entry__.build() runs)
 #   build.sh --lab      measurement build with -DB2S_LAB (B2S_LAB_* environment switches that change results: skip the encoder, drop the
@@ -45,4 +45,6 @@ if [ "$1" != "--lab" ]; then
   satellite metrics "" metrics/dtw.hip metrics/align.hip metrics/edit.hip
   # mel-cepstral distortion after DTW (include/b2s_mcd.h); contraction off, the definition rounds every product and sum on its own
   satellite mcd "-ffp-contract=off" mcd/mcd.hip
+  # YIN pitch tracking and the F0 error after DTW (include/b2s_f0.h); contraction off, the exact sums use explicit fma()
+  satellite f0 "-ffp-contract=off" f0/f0.hip
 fi
