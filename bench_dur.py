@@ -27,18 +27,13 @@ import time
 import numpy as np
 import torch
 
-from benchtime import time_calls
+from benchtime import stat, time_calls
 import bench_align
 
 B, S, T = bench_align.B, bench_align.S, bench_align.T
 BUDGET = 1.0
 CLOCK_HZ, CHAIN_INSTR, ISSUE_CYC, BLOCK = 2.4e9, 6, 4, 16
 BYTES_PER_CYC_CU = 10.0
-
-
-def stat(t):
-    med, lo, hi = t
-    return {"ms": round(med, 4), "ms_min": round(lo, 4), "ms_max": round(hi, 4)}
 
 
 def workload(maps, enc, dec, runs, warmup):

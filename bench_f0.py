@@ -22,7 +22,7 @@ import time
 import numpy as np
 import torch
 
-from benchtime import time_calls
+from benchtime import stat, time_calls
 
 SR, HOP, WIN = 16000, 200, 800
 FP64_FMA_PER_S = 78.6e12 / 2
@@ -49,11 +49,6 @@ def speechlike(lengths, seed):
             pos += n
         out[b, :L] = 0.5 * w
     return out
-
-
-def stat(t):
-    med, lo, hi = t
-    return {"ms": round(med, 4), "ms_min": round(lo, 4), "ms_max": round(hi, 4)}
 
 
 def workload(lengths, runs, warmup, seed):

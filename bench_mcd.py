@@ -19,11 +19,12 @@ import time
 import numpy as np
 import torch
 
-from benchtime import time_calls
+from benchtime import stat, time_calls
 
 from bench_dtw import make_batch
 
 ORDER = 13
+KEY = ("ms_per_batch", 3)            # this benchmark's name and digits for stat's median
 
 
 def cpu_baseline(preds, pl, targets, tl, n=3):
@@ -34,11 +35,6 @@ def cpu_baseline(preds, pl, targets, tl, n=3):
     return {"what": "NumPy restatement (voiced frames, cepstra, pure Python fastdtw radius 1, score), first %d pairs on one core, "
                     "scaled to the batch (not measured at batch size)" % n,
             "s_per_pair": round(s / n, 3), "s_per_batch_scaled": round(s / n * len(pl), 2)}
-
-
-def stat(t):
-    med, lo, hi = t
-    return {"ms_per_batch": round(med, 3), "ms_min": round(lo, 3), "ms_max": round(hi, 3)}
 
 
 def main():
@@ -56,16 +52,16 @@ def main():
     res = {"bench": "mcd", "device": torch.cuda.get_device_name(0), "B": len(pl), "n_mels": int(preds.shape[2]), "order": ORDER,
            "frames_x": int(sum(pl)), "frames_y": int(sum(tl)), "gate_ratio_r1": 1.25}
 
-    res["mcd_dtw_r1"] = stat(time_calls(lambda: mcd.mcd_dtw_batch(dp, pl, dt, tl, order=ORDER, radius=1), a.runs, a.warmup))
+    res["mcd_dtw_r1"] = stat(time_calls(lambda: mcd.mcd_dtw_batch(dp, pl, dt, tl, order=ORDER, radius=1), a.runs, a.warmup), *KEY)
     m = mcd.mcd_dtw_batch(dp, pl, dt, tl, order=ORDER, radius=1).cpu().numpy()
     if not np.all(np.isfinite(m)):
         raise RuntimeError("non-finite MCD in the benchmark batch")
     res["mcd_dtw_r1"]["mean_mcd_db"] = round(float(m.mean()), 6)
-    res["mse_dtw_r1"] = stat(time_calls(lambda: metrics.mse_dtw_batch(dp, pl, dt, tl, radius=1), a.runs, a.warmup))
+    res["mse_dtw_r1"] = stat(time_calls(lambda: metrics.mse_dtw_batch(dp, pl, dt, tl, radius=1), a.runs, a.warmup), *KEY)
     res["ratio_r1"] = round(res["mcd_dtw_r1"]["ms_per_batch"] / res["mse_dtw_r1"]["ms_per_batch"], 3)
     res["mcd_dtw_exact"] = stat(time_calls(lambda: mcd.mcd_dtw_batch(dp, pl, dt, tl, order=ORDER, radius=None),
-                                           max(5, a.runs // 4), 1))
-    res["dtw_exact"] = stat(time_calls(lambda: metrics.dtw_batch(dp, pl, dt, tl, radius=None), max(5, a.runs // 4), 1))
+                                           max(5, a.runs // 4), 1), *KEY)
+    res["dtw_exact"] = stat(time_calls(lambda: metrics.dtw_batch(dp, pl, dt, tl, radius=None), max(5, a.runs // 4), 1), *KEY)
 
     # the two new steps alone, on device-resident packed rows
     xr, xo, mx = mcd.pack_batch(dp, pl)

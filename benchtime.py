@@ -1,6 +1,6 @@
-"""What the side benchmarks (bench_align, bench_cer, bench_dtw, bench_mcd, bench_prep, bench_resample, bench_trim, bench_vocoder)
-share: importing this module puts the repository root, the package directory and tests/ (the NumPy restatements) on sys.path, and
-time_calls is their device-event timer."""
+"""What the side benchmarks (bench_align, bench_cer, bench_dtw, bench_dur, bench_f0, bench_mcd, bench_prep, bench_resample,
+bench_trim, bench_vocoder) share: importing this module puts the repository root, the package directory and tests/ (the NumPy
+restatements) on sys.path, time_calls is their device-event timer and stat the JSON shape of its answer."""
 import os
 import sys
 
@@ -28,3 +28,9 @@ def time_calls(fn, runs, warmup):
         b.synchronize()
         ms.append(a.elapsed_time(b))
     return float(np.median(ms)), float(min(ms)), float(max(ms))
+
+
+def stat(t, key="ms", digits=4):
+    """time_calls' answer as the dict a benchmark prints: the median under `key`, then ms_min and ms_max."""
+    med, lo, hi = t
+    return {key: round(med, digits), "ms_min": round(lo, digits), "ms_max": round(hi, digits)}

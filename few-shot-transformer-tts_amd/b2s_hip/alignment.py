@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import metrics, ragged
-from .cbind import B2SError, choice, dptr as p
+from .cbind import B2SError, choice, dptr as p, stream
 
 STAT_NAMES = ("backward_steps", "max_jump", "positions_visited", "last_position")
 MAX_LAYERS = 16
@@ -31,16 +31,6 @@ def mode(hp=None):
 def chunk():
     """Decoder frames per workgroup of the reduction kernel (scores are summed per chunk, then over the chunks in order)."""
     return int(metrics.load().b2s_met_align_chunk())
-
-
-def _lengths_i32(lengths, B, device, what):
-    if isinstance(lengths, torch.Tensor):
-        t = lengths.detach().reshape(-1)
-    else:
-        t = torch.from_numpy(np.asarray([int(n) for n in np.asarray(lengths).reshape(-1)], dtype=np.int32))
-    if t.numel() != B:
-        raise B2SError("%d %s for a batch of %d" % (t.numel(), what, B))
-    return t.to(device=device, dtype=torch.int32, non_blocking=True).contiguous()
 
 
 def select_alignments(encdec, input_lengths, generated_lengths, want_maps=True):
@@ -60,7 +50,7 @@ def select_alignments(encdec, input_lengths, generated_lengths, want_maps=True):
     device = ragged.device("the DTW metric", encdec[0])
     layers = []
     for a in encdec:
-        t = a.detach() if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))
+        t = ragged.as_tensor(a)
         if t.dim() != 4 or (layers and t.shape != layers[0].shape):
             raise B2SError("every layer must be [B, H, S, T] of one shape (got %s)" % (tuple(t.shape),))
         layers.append(t.to(device=device, dtype=torch.float32).contiguous())
@@ -68,8 +58,8 @@ def select_alignments(encdec, input_lengths, generated_lengths, want_maps=True):
     L = len(layers)
     nbytes = lib.b2s_met_align_ws_bytes(B, L, H, S, T)
     ws = metrics.workspace(nbytes, device)
-    enc = _lengths_i32(input_lengths, B, device, "input_lengths")
-    dec = _lengths_i32(generated_lengths, B, device, "generated_lengths")
+    enc = ragged.lengths_i32(input_lengths, B, device, "input_lengths")
+    dec = ragged.lengths_i32(generated_lengths, B, device, "generated_lengths")
     scores = torch.empty(B, L, H, dtype=torch.float64, device=device)
     best = torch.empty(B, dtype=torch.int32, device=device)
     maps = torch.empty(B, S, T, dtype=torch.float32, device=device) if want_maps else None
@@ -77,9 +67,8 @@ def select_alignments(encdec, input_lengths, generated_lengths, want_maps=True):
     stats = torch.empty(B, 4, dtype=torch.int32, device=device)
     table = (C.c_void_p * L)(*[t.data_ptr() for t in layers])          # host array: the pointers travel in the kernel arguments
     with torch.cuda.device(device):
-        stream = torch.cuda.current_stream(device).cuda_stream
         metrics.check(lib.b2s_met_align_select(C.cast(table, C.c_void_p), L, B, H, S, T, p(enc), p(dec), p(scores), p(best), p(maps),
-                                               p(paths), p(stats), p(ws), nbytes, stream))
+                                               p(paths), p(stats), p(ws), nbytes, stream(device)))
     has = best >= 0
     safe = best.clamp(min=0).to(torch.int64)
     top = scores.reshape(B, L * H).gather(1, safe.unsqueeze(1)).squeeze(1)

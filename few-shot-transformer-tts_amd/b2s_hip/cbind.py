@@ -1,5 +1,6 @@
-"""What every ctypes binding of the package shares: the loader of one shared library (Library), the device-pointer helper (dptr)
-and the opt-in switches of the reference's eval (choice, rebind).
+"""What every ctypes binding of the package shares: the loader of one shared library (Library), the device-pointer and stream
+helpers (dptr, nptr, stream), the status words of the per-item results with their raiser (OK / EMPTY / FAILED, raise_failed), the
+default hyper-parameters (default_hp) and the opt-in switches of the reference's eval (choice, rebind).
 
 torch is imported inside the calls that need it, never at module import: lib.py sets GPU_MAX_HW_QUEUES before its own torch import,
 and importing this module first must not change that order.
@@ -8,6 +9,9 @@ import ctypes as C
 import os
 import sys
 
+import numpy as np
+
+OK, EMPTY, FAILED = 0, 1, 2                # status word of one item of a batch, in every satellite library
 _PACKAGE_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -59,13 +63,37 @@ def dptr(t, empty_null=False):
     return C.c_void_p(t.data_ptr())
 
 
+def nptr(t):
+    """dptr that is NULL for a tensor without elements too: what the entry points that check their sizes themselves take."""
+    return dptr(t, empty_null=True)
+
+
+def stream(device):
+    """The current torch stream of `device` as the hipStream_t argument of an entry point (lib.stream is the hot path's variant for
+    the current device)."""
+    import torch
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def raise_failed(status, what, items="pairs", why="offsets inconsistent with the sizes"):
+    """B2SError naming the `items` whose status word (tensor or array [B]) is FAILED; nothing happens without one."""
+    bad = np.nonzero(np.asarray(status.cpu() if hasattr(status, "cpu") else status) == FAILED)[0]
+    if len(bad):
+        raise B2SError("%s failed for %s %s (%s)" % (what, items, bad.tolist(), why))
+
+
+def default_hp(hp=None):
+    """`hp`, or the global hyper-parameters for None."""
+    if hp is None:
+        from hyperparams import hparams as hp
+    return hp
+
+
 # ------------------------------------------------------------------------------------------------- opt-ins of the reference's eval
 
 def choice(hp, name):
     """hp.<name> (hp=None: the global hyper-parameters), checked: "reference" or "hip"; anything else is a ValueError."""
-    if hp is None:
-        from hyperparams import hparams as hp
-    value = getattr(hp, name)
+    value = getattr(default_hp(hp), name)
     if value not in ("reference", "hip"):
         raise ValueError("unknown %s %r (expected 'reference' or 'hip')" % (name, value))
     return value

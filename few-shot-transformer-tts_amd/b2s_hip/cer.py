@@ -29,8 +29,8 @@ import unicodedata
 import numpy as np
 import torch
 
-from . import metrics, ragged
-from .cbind import B2SError, choice, dptr as p, rebind
+from . import metrics, ragged, rescore
+from .cbind import B2SError, choice, dptr as p, rebind, stream
 
 OP_NAMES = ("sub", "del", "ins")
 
@@ -122,9 +122,8 @@ def _run(a, b, return_ops):
         return dist, ops
     status = torch.empty(n, dtype=torch.int32, device=device)
     with torch.cuda.device(device):
-        stream = torch.cuda.current_stream(device).cuda_stream
         metrics.check(lib.b2s_met_edit_distance(p(a.symbols), p(a.offsets_d), int(a.offsets[-1]), a.max_len, p(b.symbols),
-                                                p(b.offsets_d), int(b.offsets[-1]), b.max_len, n, p(dist), p(ops), p(status), stream))
+                                                p(b.offsets_d), int(b.offsets[-1]), b.max_len, n, p(dist), p(ops), p(status), stream(device)))
     failed = torch.nonzero(status != metrics.OK).reshape(-1)
     if failed.numel():
         raise B2SError("edit distance failed for pairs %s (offsets inconsistent with the sizes)" % failed.cpu().tolist())
@@ -245,14 +244,9 @@ def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m b2s_hip.cer", description="Re-score a transcriptions.jsonl on the GPU.")
     ap.add_argument("path", help="transcriptions.jsonl written by eval.py")
     ap.add_argument("--renormalize", action="store_true", help="apply basic_normalize again before scoring")
-    ap.add_argument("--json", metavar="OUT", help="also write the summary, with the per-record scores, to OUT")
+    rescore.add_arguments(ap, "--json")
     a = ap.parse_args(argv)
-    res = score_transcriptions(a.path, renormalize=a.renormalize)
-    if a.json:
-        with open(a.json, "w", encoding="utf-8") as f:
-            json.dump(res, f, ensure_ascii=False, indent=1)
-    print(json.dumps({k: v for k, v in res.items() if k != "cers"}, ensure_ascii=False, indent=1))
-    return 0
+    return rescore.finish(score_transcriptions(a.path, renormalize=a.renormalize), a.json, ("cers",), indent=1)
 
 
 if __name__ == "__main__":

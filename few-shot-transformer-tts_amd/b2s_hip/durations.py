@@ -26,10 +26,12 @@ import zipfile
 import numpy as np
 import torch
 
-from . import alignment, ragged
-from .cbind import B2SError, Library, dptr
+from . import alignment, ragged, rescore
+from .cbind import EMPTY, FAILED, OK  # noqa: F401 (the status words are part of this module's surface)
+from .cbind import B2SError, Library, dptr, nptr, stream
+from .ragged import as_tensor, lengths_i32
 
-OK, EMPTY, FAILED, SHORT = 0, 1, 2, 3
+SHORT = 3                                  # after OK, EMPTY, FAILED: fewer decoder frames than input bytes
 STATUS_NAMES = ("OK", "EMPTY", "FAILED", "SHORT")
 MAX_S = 1024
 COUNTS = ("n", "sum_x", "sum_y", "sum_abs", "sum_sq", "sum_xx", "sum_yy", "sum_xy", "max_x", "max_y", "zero_x", "zero_y")
@@ -48,29 +50,8 @@ _LIB = Library("libb2s_dur.so", _PROTOS, "b2s_dur_last_error")
 LIB_PATH, EXPORTS, load, check, workspace = _LIB.path, _LIB.exports, _LIB.load, _LIB.check, _LIB.workspace
 
 
-def _ptr(t):
-    return dptr(t, empty_null=True)
-
-
 def _device(*arrays):
     return ragged.device("the duration search", *arrays)
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
-
-
-def _tensor(a):
-    return a.detach() if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))
-
-
-def _lengths_i32(lengths, B, device, what):
-    """B lengths (list, array or tensor on any device) -> int32 device tensor; they are not clamped: the library reports a length
-    outside its range as FAILED."""
-    t = _tensor(lengths).reshape(-1)
-    if t.numel() != B:
-        raise B2SError("%d %s for a batch of %d" % (t.numel(), what, B))
-    return t.to(device=device, dtype=torch.int32).contiguous()
 
 
 # --------------------------------------------------------------------------------------------------------------------- the search
@@ -83,13 +64,13 @@ def mas_batch(maps, input_lengths, dec_lengths):
     select_alignments' focus."""
     lib = load()
     device = _device(maps)
-    t = _tensor(maps)
+    t = as_tensor(maps)
     if t.dim() != 3:
         raise B2SError("maps must be [B, S, T], got %s" % (tuple(t.shape),))
     t = t.to(device=device, dtype=torch.float32).contiguous()
     B, S, T = (int(v) for v in t.shape)
-    enc = _lengths_i32(input_lengths, B, device, "input_lengths")
-    dec = _lengths_i32(dec_lengths, B, device, "dec_lengths")
+    enc = lengths_i32(input_lengths, B, device, "input_lengths")
+    dec = lengths_i32(dec_lengths, B, device, "dec_lengths")
     path = torch.empty(B, T, dtype=torch.int32, device=device)
     durations = torch.empty(B, S, dtype=torch.int32, device=device)
     score = torch.empty(B, dtype=torch.float64, device=device)
@@ -98,8 +79,8 @@ def mas_batch(maps, input_lengths, dec_lengths):
         nbytes = lib.b2s_dur_ws_bytes(B, S, T)
         ws = workspace(nbytes, device)
         with torch.cuda.device(device):
-            check(lib.b2s_dur_mas(_ptr(t), _ptr(enc), _ptr(dec), B, S, T, _ptr(path), _ptr(durations), _ptr(score), _ptr(status),
-                                  dptr(ws), nbytes, _stream(device)))
+            check(lib.b2s_dur_mas(nptr(t), nptr(enc), nptr(dec), B, S, T, nptr(path), nptr(durations), nptr(score), nptr(status),
+                                  dptr(ws), nbytes, stream(device)))
     return {"path": path, "durations": durations, "score": score, "status": status,
             "mono_focus": score / dec.clamp(min=1).to(torch.float64)}
 
@@ -121,11 +102,11 @@ def code_point_groups(inputs, input_lengths):
     """Unit ids for the duration error per character: inputs [B, S] byte ids of utils/text.py (array or tensor; the result stays on
     the tensor's device).  A UTF-8 continuation byte (0x80..0xBF) joins the unit of the byte before it; every other id, sos and eos
     included, starts a unit.  -> [B, S] int32, non-decreasing from 0 over each utterance's length and -1 past it."""
-    ids = _tensor(inputs)
+    ids = as_tensor(inputs)
     if ids.dim() != 2:
         raise B2SError("inputs must be [B, S], got %s" % (tuple(ids.shape),))
     B, S = int(ids.shape[0]), int(ids.shape[1])
-    n = _tensor(input_lengths).reshape(-1).to(device=ids.device, dtype=torch.int64)
+    n = as_tensor(input_lengths).reshape(-1).to(device=ids.device, dtype=torch.int64)
     if n.numel() != B:
         raise B2SError("%d input_lengths for a batch of %d" % (n.numel(), B))
     starts = ~((ids >= 0x80) & (ids <= 0xBF))
@@ -174,21 +155,21 @@ def duration_error_batch(dur_x, dur_y, input_lengths, groups=None, frame_ms=None
     if frame_ms is None:
         from hyperparams import hparams as hp
         frame_ms = hp.frame_shift_ms
-    x, y = (_tensor(d).to(device=device, dtype=torch.int32).contiguous() for d in (dur_x, dur_y))
+    x, y = (as_tensor(d).to(device=device, dtype=torch.int32).contiguous() for d in (dur_x, dur_y))
     if x.dim() != 2 or x.shape != y.shape:
         raise B2SError("dur_x and dur_y must be [B, S] of one shape (got %s and %s)" % (tuple(x.shape), tuple(y.shape)))
     B, S = int(x.shape[0]), int(x.shape[1])
     g = None
     if groups is not None:
-        g = _tensor(groups).to(device=device, dtype=torch.int32).contiguous()
+        g = as_tensor(groups).to(device=device, dtype=torch.int32).contiguous()
         if g.shape != x.shape:
             raise B2SError("groups must have the shape of the durations %s (got %s)" % (tuple(x.shape), tuple(g.shape)))
-    enc = _lengths_i32(input_lengths, B, device, "input_lengths")
+    enc = lengths_i32(input_lengths, B, device, "input_lengths")
     counts = torch.zeros(B, len(COUNTS), dtype=torch.int64, device=device)
     status = torch.empty(B, dtype=torch.int32, device=device)
     if B:
         with torch.cuda.device(device):
-            check(lib.b2s_dur_score(_ptr(x), _ptr(y), _ptr(enc), dptr(g), B, S, _ptr(counts), _ptr(status), _stream(device)))
+            check(lib.b2s_dur_score(nptr(x), nptr(y), nptr(enc), dptr(g), B, S, nptr(counts), nptr(status), stream(device)))
     out = {"counts": counts, "status": status}
     out.update(scores_from_counts(counts.cpu().numpy(), frame_ms))
     return out
@@ -210,7 +191,7 @@ def teacher_forced_durations(model, batch):
     if device.type != "cuda":
         raise B2SError("the duration search runs on the GPU only; the model is on %s" % device)
     keys = ("inputs", "input_lengths", "mel_targets", "target_lengths", "input_spk_ids", "input_language_vecs")
-    args = {k: (None if batch.get(k) is None else _tensor(batch[k]).to(device)) for k in keys}
+    args = {k: (None if batch.get(k) is None else as_tensor(batch[k]).to(device)) for k in keys}
     was_training = model.training
     model.eval()
     try:
@@ -230,17 +211,17 @@ def eval_durations(model, batch, results):
     and per code point, x = generated, y = target) and `status` [B] int32 on the device: the first status that is not OK among the
     generated side's, the target side's and the error's.  Where it is not OK the scores of `bytes` and `chars` are NaN."""
     device = _model_device(model)
-    n_in = _tensor(results["input_lengths"] if results.get("input_lengths") is not None else batch["input_lengths"])
+    n_in = as_tensor(results["input_lengths"] if results.get("input_lengths") is not None else batch["input_lengths"])
     gen = byte_durations(results["alignments"]["encdec"], n_in, results["generated_lengths"])
     selected = results["alignments"].get("selected") if isinstance(results["alignments"], dict) else None
     if selected is not None:                                  # the map was chosen inside eval_batch: that choice is the one to report
         for k in ("layer", "head", "focus"):
-            gen[k] = _tensor(selected[k]).to(device)
+            gen[k] = as_tensor(selected[k]).to(device)
     tgt = teacher_forced_durations(model, batch)
     if gen["durations"].shape != tgt["durations"].shape:
         raise B2SError("the synthesized side has durations %s, the target side %s" % (tuple(gen["durations"].shape),
                                                                                      tuple(tgt["durations"].shape)))
-    groups = code_point_groups(_tensor(batch["inputs"]).to(device), n_in)
+    groups = code_point_groups(as_tensor(batch["inputs"]).to(device), n_in)
     out = {"generated": gen, "target": tgt, "groups": groups}
     status = torch.where(gen["status"] != OK, gen["status"], tgt["status"])
     for name, g in (("bytes", None), ("chars", groups)):
@@ -291,6 +272,7 @@ def extract(model, rows, mels, hp, spk_ids, lang_ids, out_dir, batch=32, units="
     return records
 
 
+@rescore.cli
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(prog="python -m b2s_hip.durations",
@@ -303,18 +285,13 @@ def main(argv=None):
     ap.add_argument("--units", default="bytes", help="bytes (one duration per input id) or chars (per UTF-8 code point)")
     ap.add_argument("--hparams", default="", help="hyper-parameter overrides, 'name=value,...'")
     a = ap.parse_args(argv)
-    if a.batch < 1:
-        print("--batch must be >= 1 (got %d)" % a.batch, file=sys.stderr)
-        return 2
+    rescore.batch(a.batch)
     if a.units not in ("bytes", "chars"):
-        print("--units must be 'bytes' or 'chars' (got %r)" % a.units, file=sys.stderr)
-        return 2
+        raise rescore.UsageError("--units must be 'bytes' or 'chars' (got %r)" % a.units)
     zipfilepath = os.path.join(a.data_dir, "mels.zip")
     meta = a.meta or os.path.join(a.data_dir, "metadata.eval.txt")
     for what, path in (("checkpoint", a.checkpoint), ("mels.zip", zipfilepath), ("metadata", meta)):
-        if not os.path.isfile(path):
-            print("%s not found: %s" % (what, path), file=sys.stderr)
-            return 2
+        rescore.found(what, path)
     from hyperparams import hparams as hp
     if a.hparams:
         hp.parse(a.hparams)
@@ -325,8 +302,7 @@ def main(argv=None):
             with open(path, encoding="utf-8") as f:
                 ids[name] = json.load(f)
         elif hp.multi_speaker or hp.multi_lingual:
-            print("%s not found: %s" % (name, path), file=sys.stderr)
-            return 2
+            rescore.found(name, path)
     from transformer.tacotron import Tacotron
     from utils.checkpoint import load_model
     from . import corpus

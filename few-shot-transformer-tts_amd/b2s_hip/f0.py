@@ -13,19 +13,16 @@ exact integer, so the results are bit-reproducible and the same for a pair alone
 re-scores a finished eval: every EVAL_DIR/<name>.npy against member <name>.npy of mels.zip, both sides vocoded by mel2wav_batch.
 """
 import ctypes as C
-import json
 import math
-import os
 import sys
 
 import numpy as np
 import torch
 
-from . import mcd, ragged
-from .cbind import B2SError, Library, dptr
-from .vocoder import _hp, mel2wav_batch
+from . import mcd, ragged, rescore
+from .cbind import EMPTY, FAILED, OK, B2SError, Library, default_hp, nptr, raise_failed, stream
+from .vocoder import mel2wav_batch
 
-OK, EMPTY, FAILED = 0, 1, 2
 MAX_WIN, MAX_TAU = 2048, 512
 SCORES = ("rmse_hz", "rmse_cents", "vde", "gpe", "ffe")
 COUNTS = ("steps", "vuv", "both", "gross")
@@ -44,23 +41,15 @@ _LIB = Library("libb2s_f0.so", _PROTOS, "b2s_f0_last_error")
 LIB_PATH, EXPORTS, load, check = _LIB.path, _LIB.exports, _LIB.load, _LIB.check
 
 
-def _ptr(t):
-    return dptr(t, empty_null=True)
-
-
 def _device(*arrays):
     return ragged.device("the F0 tracker", *arrays)
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 def yin_params(hp=None, win=None, hop=None, tau_min=None, tau_max=None, fmin=60.0, fmax=500.0, threshold=0.1, silence_db=-40.0,
                sr=None):
     """The estimator's parameters as a dict, checked.  Defaults: win = hp.win_length, hop = hp.hop_length, tau_min = ceil(sr / fmax),
     tau_max = floor(sr / fmin), threshold 0.1, min_energy = ceil(win * (32767 * 10^(silence_db / 20))^2) (silence_db=None: 0)."""
-    hp = _hp(hp) if None in (win, hop, sr) else hp
+    hp = default_hp(hp) if None in (win, hop, sr) else hp
     sr = float(hp.sr if sr is None else sr)
     win = int(hp.win_length if win is None else win)
     hop = int(hp.hop_length if hop is None else hop)
@@ -89,7 +78,7 @@ def _wav_batch(wavs, lengths, device, dtype, what="wavs"):
     """Padded [B, Lmax] array or tensor, or a list of 1-D arrays (lengths=None: their own) -> (contiguous [B, Lmax] device tensor of
     `dtype`, lengths as Python ints)."""
     if isinstance(wavs, (list, tuple)):
-        rows = [torch.as_tensor(np.asarray(w) if not isinstance(w, torch.Tensor) else w).reshape(-1) for w in wavs]
+        rows = [ragged.as_tensor(w).reshape(-1) for w in wavs]
         n = [int(r.numel()) for r in rows]
         t = torch.zeros(len(rows), max(n + [0]), dtype=dtype, device=device)
         for i, r in enumerate(rows):
@@ -97,7 +86,7 @@ def _wav_batch(wavs, lengths, device, dtype, what="wavs"):
         if lengths is None:
             return t, n
         wavs = t
-    t = torch.from_numpy(np.asarray(wavs)) if not isinstance(wavs, torch.Tensor) else wavs.detach()
+    t = ragged.as_tensor(wavs)
     if t.dim() != 2:
         raise B2SError("%s must be [B, Lmax], got %s" % (what, tuple(t.shape)))
     if lengths is None:
@@ -126,7 +115,7 @@ def quantize_batch(wavs, lengths=None):
     status = torch.empty(B, dtype=torch.int32, device=device)
     if B:
         lens = torch.tensor(n, dtype=torch.int32).to(device)
-        check(lib.b2s_f0_quantize(_ptr(wav), _ptr(lens), B, Lmax, _ptr(pcm), _ptr(peak), _ptr(status), _stream(device)))
+        check(lib.b2s_f0_quantize(nptr(wav), nptr(lens), B, Lmax, nptr(pcm), nptr(peak), nptr(status), stream(device)))
     return {"pcm": pcm, "peak": peak, "status": status, "lengths": n}
 
 
@@ -157,9 +146,9 @@ def yin_batch(wavs_or_pcm, lengths=None, hp=None, return_cmnd=False, **params):
     status = torch.empty(B, dtype=torch.int32, device=device)
     if B:
         lens = torch.tensor(n, dtype=torch.int32).to(device)
-        check(lib.b2s_f0_yin(_ptr(pcm), _ptr(lens), _ptr(off), total, B, Lmax, prm["win"], prm["hop"], prm["tau_min"], prm["tau_max"],
-                             prm["threshold"], prm["min_energy"], prm["sr"], _ptr(f0), _ptr(tau), _ptr(aper), _ptr(cm), _ptr(status),
-                             _stream(device)))
+        check(lib.b2s_f0_yin(nptr(pcm), nptr(lens), nptr(off), total, B, Lmax, prm["win"], prm["hop"], prm["tau_min"], prm["tau_max"],
+                             prm["threshold"], prm["min_energy"], prm["sr"], nptr(f0), nptr(tau), nptr(aper), nptr(cm), nptr(status),
+                             stream(device)))
         if qstatus is not None:
             status = torch.maximum(status, qstatus)
     out = {"f0": f0, "tau": tau, "aper": aper, "frame_offsets": off_h, "frame_offsets_device": off, "frames": frames,
@@ -190,11 +179,11 @@ def score_packed(x, y, kept_x, kx_offsets, kept_y, ky_offsets, path, path_offset
     scores = torch.empty(B, 5, dtype=torch.float64, device=device)
     counts = torch.empty(B, 4, dtype=torch.int32, device=device)
     status = torch.empty(B, dtype=torch.int32, device=device)
-    check(lib.b2s_f0_score(_ptr(x["f0"]), _ptr(x["tau"]), _ptr(x["frame_offsets_device"]), int(x["f0"].numel()),
-                           _ptr(y["f0"]), _ptr(y["tau"]), _ptr(y["frame_offsets_device"]), int(y["f0"].numel()),
-                           _ptr(kept_x), _ptr(kx_offsets), int(kept_x.numel()), _ptr(kept_y), _ptr(ky_offsets), int(kept_y.numel()),
-                           B, _ptr(path), _ptr(path_offsets), int(path.shape[0]), _ptr(path_len), _ptr(dtw_status),
-                           float(gross_ratio), _ptr(scores), _ptr(counts), _ptr(status), _stream(device)))
+    check(lib.b2s_f0_score(nptr(x["f0"]), nptr(x["tau"]), nptr(x["frame_offsets_device"]), int(x["f0"].numel()),
+                           nptr(y["f0"]), nptr(y["tau"]), nptr(y["frame_offsets_device"]), int(y["f0"].numel()),
+                           nptr(kept_x), nptr(kx_offsets), int(kept_x.numel()), nptr(kept_y), nptr(ky_offsets), int(kept_y.numel()),
+                           B, nptr(path), nptr(path_offsets), int(path.shape[0]), nptr(path_len), nptr(dtw_status),
+                           float(gross_ratio), nptr(scores), nptr(counts), nptr(status), stream(device)))
     return scores, counts, status
 
 
@@ -214,7 +203,7 @@ def _vocode(mels, lengths, device, n_iter, hp):
     """mel2wav_batch on the utterances of at least 2 frames; the others get an empty waveform.  -> ([B, Lmax] f32, lengths)."""
     t = ragged.as_batch(mels, device, "mels")
     n = ragged.lengths(lengths, int(t.shape[0]), int(t.shape[1]), "lengths")
-    hop = int(_hp(hp).hop_length)
+    hop = int(default_hp(hp).hop_length)
     wl = [hop * (v - 1) if v >= 2 else 0 for v in n]
     wav = torch.zeros(len(n), max(wl + [0]), dtype=torch.float32, device=device)
     sel = [b for b, v in enumerate(n) if v >= 2]
@@ -234,7 +223,7 @@ def f0_dtw_details(preds, pred_lengths, targets, target_lengths, pred_wavs=None,
     raised), x / y (the yin_batch results: pcm, f0, tau, aper, frame_offsets, ...), kept_x / kept_y with kept_offsets_x /
     kept_offsets_y, path, path_offsets (host), path_len, and `mcd`, the details of the MCD call.  An utterance of fewer than 2 frames
     on a vocoded side makes its pair EMPTY."""
-    hp = _hp(hp)
+    hp = default_hp(hp)
     device = _device(preds, targets)
     d = mcd.mcd_dtw_details(preds, pred_lengths, targets, target_lengths, order=order, radius=radius, hp=hp)
     B = int(d["status"].numel())
@@ -278,10 +267,7 @@ def f0_dtw_details(preds, pred_lengths, targets, target_lengths, pred_wavs=None,
     return out
 
 
-def _raise_failed(status, what):
-    bad = np.nonzero(np.asarray(status) == FAILED)[0]
-    if len(bad):
-        raise B2SError("%s failed for pairs %s (a non-finite sample, or sizes that do not fit together)" % (what, bad.tolist()))
+_WHY_FAILED = "a non-finite sample, or sizes that do not fit together"
 
 
 def f0_dtw_batch(preds, pred_lengths, targets, target_lengths, pred_wavs=None, target_wavs=None, order=13, radius=1, n_iter=None,
@@ -296,7 +282,7 @@ def f0_dtw_batch(preds, pred_lengths, targets, target_lengths, pred_wavs=None, t
         return out
     d = f0_dtw_details(preds, pred_lengths, targets, target_lengths, pred_wavs, target_wavs, order=order, radius=radius,
                        n_iter=n_iter, hp=hp, gross_ratio=gross_ratio, **yin)
-    _raise_failed(d["status"].cpu().numpy(), "F0 after DTW")
+    raise_failed(d["status"], "F0 after DTW", why=_WHY_FAILED)
     return {k: d[k] for k in SCORES + COUNTS + ("status",)}
 
 
@@ -328,115 +314,55 @@ def score_eval_dir(eval_dir, zipfilepath, eval_meta=None, order=13, radius=1, ba
     """Score every `<name>.npy` of eval_dir against member `<name>.npy` of the mels.zip, `batch` pairs per GPU call, both sides
     vocoded.  Returns the summary dict: overall and per-language means of the five scores over the scored records (a NaN, no step
     with both sides voiced, is left out of that score's mean), the counts (scored, empty, without a target) and the records."""
-    from . import corpus
-    hp = _hp(hp)
-    batch = max(1, int(batch))
-    lang = {}
-    if eval_meta and os.path.exists(eval_meta):
-        for row in corpus.read_metadata(eval_meta, hp.data_format):
-            lang[row["n"][:-4] if row["n"].endswith(".npy") else row["n"]] = row["i"]
-    names = sorted(f[:-4] for f in os.listdir(eval_dir) if f.endswith(".npy"))
-    mels = corpus.MelZip(zipfilepath)
-    records, no_target = [], []
+    hp = default_hp(hp)
+    lang = rescore.languages(eval_meta, hp)
+    records = []
 
-    def score(part, truth):
-        n_mels = int(truth[0].shape[-1])
-        targets, tl = mcd._pad(truth, part, n_mels, "target")
-        preds, pl = mcd._pad([np.load(os.path.join(eval_dir, n + ".npy")).astype(np.float32) for n in part], part, n_mels,
-                             "generated")
+    def score(part, preds, pl, targets, tl):
         out = f0_dtw_details(preds, pl, targets, tl, order=order, radius=radius, n_iter=n_iter, hp=hp, **yin)
-        _raise_failed(out["status"].cpu().numpy(), "F0 after DTW")
+        raise_failed(out["status"], "F0 after DTW", why=_WHY_FAILED)
         for n, r in zip(part, _records(out)):
             rec = {"name": n, "language": lang.get(n), "scored": r is not None}
             rec.update(r if r is not None else dict.fromkeys(SCORES + COUNTS))
             records.append(rec)
-    try:
-        part, truth = [], []
-        for n in names:
-            try:
-                truth.append(mels.load(n + ".npy").astype(np.float32))
-            except KeyError:                                   # generated, but not a member of the zip
-                no_target.append(n)
-                continue
-            part.append(n)
-            if len(part) == batch:
-                score(part, truth)
-                part, truth = [], []
-        if part:
-            score(part, truth)
-    finally:
-        mels.close()
-    scored = [r for r in records if r["scored"]]
-
-    def means(recs):
-        out = {"n": len(recs)}
-        for k in SCORES:
-            v = [r[k] for r in recs if not math.isnan(r[k])]
-            out[k] = float(np.mean(v)) if v else None
-        return out
-    languages = {}
-    for r in scored:
-        languages.setdefault(str(r["language"]), []).append(r)
+    no_target = rescore.walk(eval_dir, zipfilepath, batch, score)
+    head = {"metric": "f0_dtw", "radius": "exact" if radius is None else int(radius)}
+    res = rescore.summary(head, records, [r for r in records if r["scored"]], no_target, SCORES)
     for r in records:                                          # JSON has no NaN
         for k in SCORES:
             if r[k] is not None and math.isnan(r[k]):
                 r[k] = None
-    res = {"metric": "f0_dtw", "radius": "exact" if radius is None else int(radius), "n_scored": len(scored),
-           "n_empty": len(records) - len(scored), "n_without_target": len(no_target)}
-    res.update({k: v for k, v in means(scored).items() if k != "n"})
-    res.update({"languages": {k: means(v) for k, v in sorted(languages.items())}, "without_target": no_target, "records": records})
     return res
 
 
+@rescore.cli
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(prog="python -m b2s_hip.f0",
                                  description="Re-score a finished eval with the F0 error after DTW (YIN) on the GPU.")
-    ap.add_argument("eval_dir", help="directory of generated mels, <name>.npy as save_eval_results writes them")
-    ap.add_argument("--data-dir", required=True, help="directory of mels.zip and metadata.eval.txt")
-    ap.add_argument("--zipfilepath", help="the ground-truth mels (default: DATA_DIR/mels.zip)")
-    ap.add_argument("--eval-meta", help="metadata with the languages (default: DATA_DIR/metadata.eval.txt)")
-    ap.add_argument("--radius", default="1", help="fastdtw radius >= 1, or 'exact' for the full dtw")
-    ap.add_argument("--batch", type=int, default=64, help="pairs per GPU call")
+    rescore.add_arguments(ap, "eval_dir", "--data-dir", "--zipfilepath", "--eval-meta", "--radius", "--batch")
     ap.add_argument("--n-iter", type=int, help="Griffin-Lim iterations of the vocoder (default: hp.n_iter)")
     ap.add_argument("--fmin", type=float, default=60.0, help="lowest F0 in Hz")
     ap.add_argument("--fmax", type=float, default=500.0, help="highest F0 in Hz")
     ap.add_argument("--threshold", type=float, default=0.1, help="YIN's absolute threshold")
     ap.add_argument("--silence-db", type=float, default=-40.0, help="frames below this level (dB re full scale) are unvoiced")
-    ap.add_argument("--json", metavar="OUT", help="also write the summary, with the per-record scores, to OUT")
+    rescore.add_arguments(ap, "--json")
     a = ap.parse_args(argv)
-    zipfilepath = a.zipfilepath or os.path.join(a.data_dir, "mels.zip")
-    eval_meta = a.eval_meta or os.path.join(a.data_dir, "metadata.eval.txt")
-    try:
-        radius = None if a.radius == "exact" else int(a.radius)
-    except ValueError:
-        radius = 0
-    if radius is not None and radius < 1:
-        print("--radius must be an integer >= 1 or 'exact' (got %r)" % a.radius, file=sys.stderr)
-        return 2
-    if a.batch < 1:
-        print("--batch must be >= 1 (got %d)" % a.batch, file=sys.stderr)
-        return 2
+    zipfilepath, eval_meta = rescore.inputs(a)
+    radius = rescore.radius(a.radius)
+    rescore.batch(a.batch)
     if a.n_iter is not None and a.n_iter < 0:
-        print("--n-iter must be >= 0 (got %d)" % a.n_iter, file=sys.stderr)
-        return 2
+        raise rescore.UsageError("--n-iter must be >= 0 (got %d)" % a.n_iter)
     from hyperparams import hparams as hp
     yin = {"fmin": a.fmin, "fmax": a.fmax, "threshold": a.threshold, "silence_db": a.silence_db}
     try:
         yin_params(hp, **yin)
     except B2SError as e:
-        print("%s" % e, file=sys.stderr)
-        return 2
-    for what, path, ok in (("EVAL_DIR", a.eval_dir, os.path.isdir(a.eval_dir)), ("mels.zip", zipfilepath, os.path.isfile(zipfilepath))):
-        if not ok:
-            print("%s not found: %s" % (what, path), file=sys.stderr)
-            return 2
+        raise rescore.UsageError(str(e))
+    rescore.found("EVAL_DIR", a.eval_dir, isdir=True)
+    rescore.found("mels.zip", zipfilepath)
     res = score_eval_dir(a.eval_dir, zipfilepath, eval_meta, radius=radius, batch=a.batch, n_iter=a.n_iter, hp=hp, **yin)
-    if a.json:
-        with open(a.json, "w", encoding="utf-8") as f:
-            json.dump(res, f, ensure_ascii=False, indent=1)
-    print(json.dumps({k: v for k, v in res.items() if k not in ("records", "without_target")}, ensure_ascii=False))
-    return 0
+    return rescore.finish(res, a.json, ("records", "without_target"))
 
 
 if __name__ == "__main__":

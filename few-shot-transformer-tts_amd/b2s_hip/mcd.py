@@ -13,19 +13,15 @@ pair alone or inside a batch.  There is no CPU fallback: a missing library is an
 re-scores a finished eval: every EVAL_DIR/<name>.npy against member <name>.npy of mels.zip.
 """
 import ctypes as C
-import json
 import math
-import os
 import sys
 
 import numpy as np
 import torch
 
-from . import metrics, ragged
-from .cbind import B2SError, Library, dptr
-from .vocoder import _hp
+from . import metrics, ragged, rescore
+from .cbind import EMPTY, FAILED, OK, B2SError, Library, default_hp, nptr, raise_failed, stream
 
-OK, EMPTY, FAILED = 0, 1, 2
 MAX_MELS, MAX_ORDER = 512, 256
 LN_SCALE = math.log(10.0) / 20.0           # dB -> natural-log magnitude
 DB_SCALE = 10.0 / math.log(10.0)           # the MCD's 10 / ln 10
@@ -67,16 +63,12 @@ def _device_table(n_mels, order, device):
     return _tables[key]
 
 
-def _ptr(t):
-    return dptr(t, empty_null=True)
-
-
 def cepstra_packed(rows, offsets, max_len, order=13, hp=None):
     """b2s_mcd_cepstra on packed device rows [total, n_mels] fp32 with their B + 1 int32 device offsets; max_len bounds every length.
     No host read.  Returns device tensors: cep (a buffer of `total` rows of which the first offsets[B] are written), offsets
     [B + 1], voiced [B] and status [B]."""
     lib = load()
-    hp = _hp(hp)
+    hp = default_hp(hp)
     device = rows.device
     total, n_mels = int(rows.shape[0]), int(rows.shape[1])
     B = int(offsets.numel()) - 1
@@ -88,10 +80,9 @@ def cepstra_packed(rows, offsets, max_len, order=13, hp=None):
     off = torch.empty(B + 1, dtype=torch.int32, device=device)
     voiced = torch.empty(B, dtype=torch.int32, device=device)
     status = torch.empty(B, dtype=torch.int32, device=device)
-    stream = torch.cuda.current_stream(device).cuda_stream
-    check(lib.b2s_mcd_cepstra(_ptr(rows), _ptr(offsets), total, int(max_len), B, n_mels, order, _ptr(table),
+    check(lib.b2s_mcd_cepstra(nptr(rows), nptr(offsets), total, int(max_len), B, n_mels, order, nptr(table),
                               1 if hp.symmetric_mel else 0, float(hp.max_abs_value), float(hp.max_db), float(hp.ref_db), LN_SCALE,
-                              _ptr(cep), _ptr(off), _ptr(voiced), _ptr(status), _ptr(ws), nbytes, stream))
+                              nptr(cep), nptr(off), nptr(voiced), nptr(status), nptr(ws), nbytes, stream(device)))
     return {"cep": cep, "offsets": off, "voiced": voiced, "status": status}
 
 
@@ -105,9 +96,9 @@ def score_packed(cep_x, offsets_x, total_x, cep_y, offsets_y, total_y, path, pat
     mcd = torch.empty(B, dtype=torch.float64, device=device)
     status = torch.empty(B, dtype=torch.int32, device=device)
     dist = torch.full((tp,), float("nan"), dtype=torch.float64, device=device)
-    check(lib.b2s_mcd_score(_ptr(cep_x), _ptr(offsets_x), int(total_x), _ptr(cep_y), _ptr(offsets_y), int(total_y), B, order,
-                            _ptr(path), _ptr(path_offsets), tp, _ptr(path_len), _ptr(dtw_status), DB_SCALE, _ptr(mcd), _ptr(status),
-                            _ptr(dist), torch.cuda.current_stream(device).cuda_stream))
+    check(lib.b2s_mcd_score(nptr(cep_x), nptr(offsets_x), int(total_x), nptr(cep_y), nptr(offsets_y), int(total_y), B, order,
+                            nptr(path), nptr(path_offsets), tp, nptr(path_len), nptr(dtw_status), DB_SCALE, nptr(mcd), nptr(status),
+                            nptr(dist), stream(device)))
     return mcd, status, dist
 
 
@@ -126,12 +117,6 @@ def _pick_device(*arrays):
     return ragged.device("the DTW metric", *arrays)
 
 
-def _raise_failed(status, what):
-    bad = np.nonzero(np.asarray(status) == FAILED)[0]
-    if len(bad):
-        raise B2SError("%s failed for utterances %s (offsets inconsistent with the sizes)" % (what, bad.tolist()))
-
-
 def cepstra_batch(mels, lengths, order=13, hp=None):
     """Voiced frames of every utterance as mel cepstra c_1..c_order.  mels: padded [B, T, n_mels] NumPy array or tensor on any device
     (normalised mel scale), lengths [B].  Returns device tensors: the cepstra of the whole batch packed gap-free [total_voiced,
@@ -140,7 +125,7 @@ def cepstra_batch(mels, lengths, order=13, hp=None):
     out = cepstra_packed(rows, off_d, max_len, order, hp)
     host = torch.cat([out["offsets"], out["status"]]).cpu().numpy()
     B = len(host) // 2
-    _raise_failed(host[B + 1:], "cepstra")
+    raise_failed(host[B + 1:], "cepstra", "utterances")
     return out["cep"][:int(host[B])], out["offsets"], out["voiced"]
 
 
@@ -188,7 +173,7 @@ def mcd_dtw_batch(preds, pred_lengths, targets, target_lengths, order=13, radius
         empty = torch.empty(0, dtype=torch.float64, device=_pick_device(preds, targets))
         return (empty, []) if return_paths else empty
     out = mcd_dtw_details(preds, pred_lengths, targets, target_lengths, order=order, radius=radius, hp=hp)
-    _raise_failed(out["status"].cpu().numpy(), "MCD after DTW")
+    raise_failed(out["status"], "MCD after DTW", "utterances")
     return (out["mcd"], ragged.paths(out)) if return_paths else out["mcd"]
 
 
@@ -202,112 +187,47 @@ def calculate_mcd_dtw(preds, pred_lengths, targets, target_lengths, order=13, ra
 
 # ------------------------------------------------------------------------------------------------------- re-scoring a finished eval
 
-def _pad(mels, names, n_mels, what):
-    """Ragged list of [T, n_mels] arrays -> padded fp32 [B, max T, n_mels] and the lengths; a file of another shape is a B2SError
-    that names it."""
-    for m, name in zip(mels, names):
-        if m.ndim != 2 or int(m.shape[1]) != n_mels:
-            raise B2SError("%s %s.npy has shape %s, expected [frames, %d]" % (what, name, tuple(m.shape), n_mels))
-    n = [int(m.shape[0]) for m in mels]
-    out = np.zeros((len(mels), max(max(n), 1), n_mels), np.float32)
-    for i, m in enumerate(mels):
-        out[i, :n[i]] = m
-    return out, n
-
-
 def score_eval_dir(eval_dir, zipfilepath, eval_meta=None, order=13, radius=1, batch=64, hp=None):
     """Score every `<name>.npy` of eval_dir against member `<name>.npy` of the mels.zip, `batch` pairs per GPU call (only one
     batch of mels is in memory at a time).  Returns the summary dict: overall and per-language mean MCD over the scored records, the
     counts (scored, empty, without a target) and the per-record scores."""
-    from . import corpus
-    hp = _hp(hp)
-    batch = max(1, int(batch))
-    lang = {}
-    if eval_meta and os.path.exists(eval_meta):
-        for row in corpus.read_metadata(eval_meta, hp.data_format):
-            lang[row["n"][:-4] if row["n"].endswith(".npy") else row["n"]] = row["i"]
-    names = sorted(f[:-4] for f in os.listdir(eval_dir) if f.endswith(".npy"))
-    mels = corpus.MelZip(zipfilepath)
-    records, no_target = [], []
+    hp = default_hp(hp)
+    lang = rescore.languages(eval_meta, hp)
+    records = []
 
-    def score(part, truth):
-        n_mels = int(truth[0].shape[-1])
-        targets, tl = _pad(truth, part, n_mels, "target")
-        preds, pl = _pad([np.load(os.path.join(eval_dir, n + ".npy")).astype(np.float32) for n in part], part, n_mels, "generated")
+    def score(part, preds, pl, targets, tl):
         out = mcd_dtw_details(preds, pl, targets, tl, order=order, radius=radius, hp=hp)
         host = {k: out[k].cpu().numpy() for k in ("mcd", "status", "voiced_x", "voiced_y", "path_len")}
-        _raise_failed(host["status"], "MCD after DTW")
+        raise_failed(host["status"], "MCD after DTW", "utterances")
         for j, n in enumerate(part):
             empty = int(host["status"][j]) == EMPTY
             records.append({"name": n, "language": lang.get(n), "mcd": None if empty else float(host["mcd"][j]),
                             "voiced_pred": int(host["voiced_x"][j]), "voiced_target": int(host["voiced_y"][j]),
                             "path_len": int(host["path_len"][j])})
-    try:
-        part, truth = [], []
-        for n in names:
-            try:
-                truth.append(mels.load(n + ".npy").astype(np.float32))
-            except KeyError:                                   # generated, but not a member of the zip
-                no_target.append(n)
-                continue
-            part.append(n)
-            if len(part) == batch:
-                score(part, truth)
-                part, truth = [], []
-        if part:
-            score(part, truth)
-    finally:
-        mels.close()
-    scored = [r for r in records if r["mcd"] is not None]
-    languages = {}
-    for r in scored:
-        languages.setdefault(str(r["language"]), []).append(r["mcd"])
-    return {"metric": "mcd_dtw_db", "order": int(order), "radius": "exact" if radius is None else int(radius),
-            "n_scored": len(scored), "n_empty": len(records) - len(scored), "n_without_target": len(no_target),
-            "mcd": float(np.mean([r["mcd"] for r in scored])) if scored else None,
-            "languages": {k: {"n": len(v), "mcd": float(np.mean(v))} for k, v in sorted(languages.items())},
-            "without_target": no_target, "records": records}
+    no_target = rescore.walk(eval_dir, zipfilepath, batch, score)
+    head = {"metric": "mcd_dtw_db", "order": int(order), "radius": "exact" if radius is None else int(radius)}
+    return rescore.summary(head, records, [r for r in records if r["mcd"] is not None], no_target, ("mcd",))
 
 
+@rescore.cli
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(prog="python -m b2s_hip.mcd", description="Re-score a finished eval with MCD-DTW on the GPU.")
-    ap.add_argument("eval_dir", help="directory of generated mels, <name>.npy as save_eval_results writes them")
-    ap.add_argument("--data-dir", required=True, help="directory of mels.zip and metadata.eval.txt")
-    ap.add_argument("--zipfilepath", help="the ground-truth mels (default: DATA_DIR/mels.zip)")
-    ap.add_argument("--eval-meta", help="metadata with the languages (default: DATA_DIR/metadata.eval.txt)")
+    rescore.add_arguments(ap, "eval_dir", "--data-dir", "--zipfilepath", "--eval-meta")
     ap.add_argument("--order", type=int, default=13, help="cepstral coefficients c_1..c_order")
-    ap.add_argument("--radius", default="1", help="fastdtw radius >= 1, or 'exact' for the full dtw")
-    ap.add_argument("--batch", type=int, default=64, help="pairs per GPU call")
-    ap.add_argument("--json", metavar="OUT", help="also write the summary, with the per-record scores, to OUT")
+    rescore.add_arguments(ap, "--radius", "--batch", "--json")
     a = ap.parse_args(argv)
-    zipfilepath = a.zipfilepath or os.path.join(a.data_dir, "mels.zip")
-    eval_meta = a.eval_meta or os.path.join(a.data_dir, "metadata.eval.txt")
-    try:
-        radius = None if a.radius == "exact" else int(a.radius)
-    except ValueError:
-        radius = 0
-    if radius is not None and radius < 1:
-        print("--radius must be an integer >= 1 or 'exact' (got %r)" % a.radius, file=sys.stderr)
-        return 2
+    zipfilepath, eval_meta = rescore.inputs(a)
+    radius = rescore.radius(a.radius)
     from hyperparams import hparams as hp
     top = min(int(hp.num_mels) - 1, MAX_ORDER)
     if not 1 <= a.order <= top:
-        print("--order must be in 1..%d for %d mel bins (got %d)" % (top, int(hp.num_mels), a.order), file=sys.stderr)
-        return 2
-    if a.batch < 1:
-        print("--batch must be >= 1 (got %d)" % a.batch, file=sys.stderr)
-        return 2
-    for what, path, ok in (("EVAL_DIR", a.eval_dir, os.path.isdir(a.eval_dir)), ("mels.zip", zipfilepath, os.path.isfile(zipfilepath))):
-        if not ok:
-            print("%s not found: %s" % (what, path), file=sys.stderr)
-            return 2
-    res = score_eval_dir(a.eval_dir, zipfilepath, eval_meta, order=a.order, radius=radius, batch=a.batch)
-    if a.json:
-        with open(a.json, "w", encoding="utf-8") as f:
-            json.dump(res, f, ensure_ascii=False, indent=1)
-    print(json.dumps({k: v for k, v in res.items() if k not in ("records", "without_target")}, ensure_ascii=False))
-    return 0
+        raise rescore.UsageError("--order must be in 1..%d for %d mel bins (got %d)" % (top, int(hp.num_mels), a.order))
+    rescore.batch(a.batch)
+    rescore.found("EVAL_DIR", a.eval_dir, isdir=True)
+    rescore.found("mels.zip", zipfilepath)
+    res = score_eval_dir(a.eval_dir, zipfilepath, eval_meta, order=a.order, radius=radius, batch=a.batch, hp=hp)
+    return rescore.finish(res, a.json, ("records", "without_target"))
 
 
 if __name__ == "__main__":

@@ -14,10 +14,10 @@ import numpy as np
 import torch
 
 from . import ragged
-from .cbind import B2SError, Library, choice, dptr, rebind
+from .cbind import EMPTY, FAILED, OK  # noqa: F401 (the status words are part of this module's surface)
+from .cbind import B2SError, Library, choice, nptr, raise_failed, rebind, stream
 
 VOICED_ONLY = 1
-OK, EMPTY, FAILED = 0, 1, 2
 
 P = C.c_void_p
 _I = C.c_int
@@ -65,12 +65,9 @@ def dtw_packed(xp, xo_d, tx, mx, yp, yo_d, ty, my, B, dim, r, flags, path_offset
         path = out["path"] = torch.empty(max(1, int(path_offsets[-1])), 2, dtype=torch.int32, device=device)
         po_d = out["path_offsets_device"] = torch.from_numpy(path_offsets).to(device)
         out["path_offsets"] = path_offsets
-
-    def p(t):
-        return dptr(t, empty_null=True)
-    check(lib.b2s_met_dtw(p(xp), p(xo_d), tx, mx, p(yp), p(yo_d), ty, my, B, dim, r, flags, p(out["cost"]), p(out["mse"]),
-                          p(out["path_len"]), p(out["status"]), p(path), p(po_d), p(ws), nbytes,
-                          torch.cuda.current_stream(device).cuda_stream))
+    check(lib.b2s_met_dtw(nptr(xp), nptr(xo_d), tx, mx, nptr(yp), nptr(yo_d), ty, my, B, dim, r, flags, nptr(out["cost"]),
+                          nptr(out["mse"]), nptr(out["path_len"]), nptr(out["status"]), nptr(path), nptr(po_d), nptr(ws), nbytes,
+                          stream(device)))
     return out
 
 
@@ -93,26 +90,19 @@ def _run(x, x_lengths, y, y_lengths, radius, flags, return_paths):
                       max(ly), B, dim, r, flags, po)
 
 
-def _raise_failed(status):
-    st = status.cpu().numpy()
-    if np.any(st == FAILED):
-        raise B2SError("DTW failed for pairs %s (offsets inconsistent with the sizes)" % np.nonzero(st == FAILED)[0].tolist())
-
-
 def dtw_batch(x, x_lengths, y, y_lengths, radius=1, return_paths=False):
     """fastdtw(x_b[:lx_b], y_b[:ly_b], radius) with euclidean distance for every pair (radius=None: the exact dtw), all frames kept.
     x, y: padded [B, T, dim] (or [B, T]) NumPy arrays or tensors on any device.  Returns the costs as a float64 device tensor [B]
     (NaN where a side is empty), and with return_paths also the list of int64 [L_b, 2] host paths."""
     out = _run(x, x_lengths, y, y_lengths, radius, 0, return_paths)
-    _raise_failed(out["status"])
+    raise_failed(out["status"], "DTW")
     cost = torch.where(out["status"] == OK, out["cost"], torch.full_like(out["cost"], float("nan")))
     return (cost, ragged.paths(out)) if return_paths else cost
 
 
 def fastdtw(x, y, radius=1):
     """One pair, fastdtw's return value: (distance, [(i, j), ...]).  x, y: [T, dim] or [T]."""
-    x = x if isinstance(x, torch.Tensor) else np.asarray(x)
-    y = y if isinstance(y, torch.Tensor) else np.asarray(y)
+    x, y = ragged.as_tensor(x), ragged.as_tensor(y)
     if len(x) == 0 or len(y) == 0:
         raise B2SError("fastdtw needs two non-empty sequences")
     cost, paths = dtw_batch(x[None], [len(x)], y[None], [len(y)], radius=radius, return_paths=True)

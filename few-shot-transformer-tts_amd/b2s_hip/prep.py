@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from . import vocoder
+from .cbind import stream
 from .lib import B2SError, ptr
 
 log = logging.getLogger(__name__)
@@ -76,7 +77,7 @@ def _trim_device(wavs, lengths, gap_threshold):
     out = torch.empty(B, Lmax + LEAD + TAIL, dtype=torch.float32, device=device)
     meta = torch.empty(4, B, dtype=torch.int32, device=device)
     vocoder.check(lib.b2s_voc_prep_trim(ptr(wavs), ptr(lens), B, Lmax, int(gap_threshold), ptr(out), ptr(meta[0]), ptr(meta[1]),
-                                        ptr(meta[2]), ptr(meta[3]), ptr(ws), ws.numel(), torch.cuda.current_stream(device).cuda_stream))
+                                        ptr(meta[2]), ptr(meta[3]), ptr(ws), ws.numel(), stream(device)))
     return out, meta
 
 
@@ -142,7 +143,7 @@ def _resample_device(wavs, lengths, orig_sr):
     meta = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.array(samples, np.int32)[:, None], counts], axis=1).T)).to(device)
     out = torch.empty(B, Lmax_out, dtype=torch.float32, device=device)
     vocoder.check(lib.b2s_voc_resample(ptr(wavs), ptr(meta[0]), B, Lmax, channels, int(orig_sr), ptr(meta[1]), ptr(meta[2]), Lmax_out,
-                                       ptr(out), ptr(ws), ws.numel(), torch.cuda.current_stream(device).cuda_stream))
+                                       ptr(out), ptr(ws), ws.numel(), stream(device)))
     return out, [int(n) for n in counts[:, 1]]
 
 
@@ -175,7 +176,7 @@ def abs_quantile_batch(wavs, lengths, intervals, fraction=0.95):
     ws = vocoder.workspace(lib.b2s_voc_prep_ws_bytes(B, Lmax, WS_QUANTILE), device)
     out = torch.empty(B, dtype=torch.float32, device=device)
     vocoder.check(lib.b2s_voc_prep_abs_quantile(ptr(wavs), ptr(lens), B, Lmax, ptr(iv_dev), ptr(n_dev), NI, float(fraction), ptr(out),
-                                                ptr(ws), ws.numel(), torch.cuda.current_stream(device).cuda_stream))
+                                                ptr(ws), ws.numel(), stream(device)))
     return out.cpu().numpy()
 
 

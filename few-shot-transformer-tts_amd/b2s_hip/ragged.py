@@ -1,5 +1,5 @@
-"""Ragged batches as the satellite libraries take them: packed rows with B + 1 int32 offsets.  Shared by metrics, mcd, cer, vocoder
-and alignment."""
+"""Ragged batches as the satellite libraries take them: packed rows with B + 1 int32 offsets.  Shared by metrics, mcd, f0, durations,
+cer, vocoder and alignment."""
 import numpy as np
 import torch
 
@@ -39,9 +39,23 @@ def lengths(lengths, B, T, what):
     return [min(n, T) for n in out]                    # x[i, :n] slices past the end like the reference's indexing
 
 
+def as_tensor(a):
+    """Array, list or tensor -> tensor where it is: a tensor detached, anything else through np.asarray without a copy."""
+    return a.detach() if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))
+
+
+def lengths_i32(lengths, B, device, what):
+    """B lengths (list, array or tensor on any device) -> contiguous int32 tensor on `device`.  A wrong count is refused; nothing is
+    clamped (the library clamps, or reports a length outside its range as FAILED) and a float is cut towards zero."""
+    t = as_tensor(lengths).reshape(-1)
+    if t.numel() != B:
+        raise B2SError("%d %s for a batch of %d" % (t.numel(), what, B))
+    return t.to(device=device, dtype=torch.int32, non_blocking=True).contiguous()
+
+
 def as_batch(a, device, what):
     """[B, T, dim] (or [B, T] for dim 1) NumPy array or tensor on any device -> contiguous fp32 tensor [B, T, dim] on `device`."""
-    t = torch.from_numpy(np.asarray(a)) if not isinstance(a, torch.Tensor) else a.detach()
+    t = as_tensor(a)
     if t.dim() == 2:
         t = t.unsqueeze(-1)
     if t.dim() != 3:

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import ragged
-from .cbind import Library
+from .cbind import Library, default_hp, stream
 from .lib import B2SError, ptr
 
 WS_MEL2WAV, WS_WAV2MEL = 0, 1
@@ -48,14 +48,8 @@ _LIB = Library("libb2s_vocoder.so", _PROTOS, "b2s_voc_last_error")
 LIB_PATH, EXPORTS, load, check, workspace = _LIB.path, _LIB.exports, _LIB.load, _LIB.check, _LIB.workspace
 
 
-def _hp(hp=None):
-    if hp is None:
-        from hyperparams import hparams as hp
-    return hp
-
-
 def params(hp=None):
-    hp = _hp(hp)
+    hp = default_hp(hp)
     return Params(sr=int(hp.sr), n_fft=int(hp.n_fft), hop=int(hp.hop_length), win=int(hp.win_length), n_mels=int(hp.num_mels),
                   preemphasis=float(hp.preemphasis), ref_db=float(hp.ref_db), max_db=float(hp.max_db),
                   max_abs_value=float(hp.max_abs_value), power=float(hp.power), symmetric_mel=int(bool(hp.symmetric_mel)))
@@ -81,7 +75,7 @@ _basis_cache = {}
 
 def mel_basis(hp=None):
     """librosa.filters.mel(sr, n_fft, n_mels) (Slaney scale, htk=False, norm=1): [n_mels, 1 + n_fft // 2] float64, cached."""
-    hp = _hp(hp)
+    hp = default_hp(hp)
     key = ("basis", int(hp.sr), int(hp.n_fft), int(hp.num_mels))
     if key not in _basis_cache:
         sr, n_fft, n_mels = key[1:]
@@ -98,7 +92,7 @@ def mel_basis(hp=None):
 
 def inverse_mel_basis(hp=None):
     """np.linalg.pinv(mel_basis): [1 + n_fft // 2, n_mels] float64, cached (the reference's mel_to_linear)."""
-    hp = _hp(hp)
+    hp = default_hp(hp)
     key = ("pinv", int(hp.sr), int(hp.n_fft), int(hp.num_mels))
     if key not in _basis_cache:
         inv = np.linalg.pinv(mel_basis(hp))
@@ -123,7 +117,7 @@ def mel2wav_batch(mels, lengths, n_iter=None, hp=None):
     """Vocode a padded batch of normalised mels [B, Tmax, n_mels] (cuda tensor or NumPy) with per-utterance frame counts `lengths`
     (host sequence, every T_b >= 2).  Returns (wav [B, hop * (Tmax - 1)] cuda fp32, zero past each hop * (T_b - 1), wav_lengths).
     Runs on torch.cuda.current_stream() without synchronising; the workspace comes from the torch allocator."""
-    hp = _hp(hp)
+    hp = default_hp(hp)
     lib = load()
     n_iter = int(hp.n_iter if n_iter is None else n_iter)
     if isinstance(mels, np.ndarray):
@@ -147,7 +141,7 @@ def mel2wav_batch(mels, lengths, n_iter=None, hp=None):
     _, inv_t = _device_tables(hp, device)
     wav = torch.empty(B, int(hp.hop_length) * (Tmax - 1), dtype=torch.float32, device=device)
     check(lib.b2s_voc_mel2wav(C.byref(prm), ptr(mels), ptr(off), B, Tmax, total, n_iter, ptr(inv_t), ptr(wav), ptr(ws),
-                              ws.numel(), torch.cuda.current_stream(device).cuda_stream))
+                              ws.numel(), stream(device)))
     return wav, [int(hp.hop_length) * (t - 1) for t in frames]
 
 
@@ -155,7 +149,7 @@ def wav2mel_batch(wavs, lengths, hp=None):
     """Normalised mels of a padded batch of waveforms [B, Lmax] (cuda tensor or NumPy) with per-utterance sample counts `lengths`
     (host sequence, every L_b >= 2).  Returns (mels [B, 1 + Lmax // hop, n_mels] cuda fp32, zero past each frame count,
     frame_lengths = 1 + L_b // hop)."""
-    hp = _hp(hp)
+    hp = default_hp(hp)
     lib = load()
     if isinstance(wavs, np.ndarray):
         wavs = torch.from_numpy(np.ascontiguousarray(wavs, dtype=np.float32)).cuda()
@@ -182,7 +176,7 @@ def wav2mel_batch(wavs, lengths, hp=None):
     lens = torch.tensor(samples, dtype=torch.int32).to(device)
     mels = torch.zeros(B, Tout, int(hp.num_mels), dtype=torch.float32, device=device)
     check(lib.b2s_voc_wav2mel(C.byref(prm), ptr(wavs), ptr(lens), ptr(off), B, Lmax, total, ptr(basis), ptr(mels), ptr(ws),
-                              ws.numel(), torch.cuda.current_stream(device).cuda_stream))
+                              ws.numel(), stream(device)))
     return mels, frames
 
 
@@ -190,7 +184,7 @@ def wav2mel_batch(wavs, lengths, hp=None):
 
 def trim_params(hp=None):
     """(top_db, frame_length, hop_length) of the reference's trim_silence_intervals: 50 dB, 8 analysis windows, one frame shift."""
-    hp = _hp(hp)
+    hp = default_hp(hp)
     return 50, int(hp.sr / 1000 * hp.frame_length_ms) * 8, int(hp.sr / 1000 * hp.frame_shift_ms)
 
 
@@ -225,7 +219,7 @@ def _split_device(wavs, lengths, top_db, frame_length, hop_length, want_flags=Fa
            "wavs": wavs, "frames": frames, "shape": (B, Lmax, fl, hop)}
     check(lib.b2s_voc_silence_split(ptr(wavs), ptr(lens), B, Lmax, top_db, fl, hop, ptr(out["intervals"]), ptr(out["n"]), ptr(out["trim"]),
                                     ptr(out["prefix"]), ptr(out["out_lengths"]), ptr(out["flags"]) if want_flags else None, ptr(ws),
-                                    ws.numel(), torch.cuda.current_stream(device).cuda_stream))
+                                    ws.numel(), stream(device)))
     return out
 
 
@@ -235,7 +229,7 @@ def _gather_device(sp):
     wavs = sp["wavs"]
     wav_out = torch.empty_like(wavs)
     check(load().b2s_voc_silence_gather(ptr(wavs), B, Lmax, fl, hop, ptr(sp["intervals"]), ptr(sp["n"]), ptr(sp["prefix"]),
-                                        ptr(sp["out_lengths"]), ptr(wav_out), torch.cuda.current_stream(wavs.device).cuda_stream))
+                                        ptr(sp["out_lengths"]), ptr(wav_out), stream(wavs.device)))
     return wav_out
 
 
@@ -322,7 +316,7 @@ def get_spectrograms(wav, hp=None):
 def save_wav(wav, path, hp=None):
     """The reference's save_wav: peak-normalise by 1 / max(0.01, max|wav|) and write 16-bit PCM mono at hp.sr (what soundfile
     writes for .wav by default), through the stdlib `wave` module."""
-    hp = _hp(hp)
+    hp = default_hp(hp)
     wav = np.asarray(wav, dtype=np.float64).reshape(-1)
     scaled = wav / max(0.01, float(np.max(np.abs(wav))) if wav.size else 0.0)
     pcm = np.round(np.clip(scaled, -1.0, 1.0) * 32767).astype("<i2")

@@ -1,5 +1,5 @@
-"""CPU-only tests of what the bindings share: the loader (b2s_hip.cbind.Library), the workspace and pointer helpers, the ragged-batch
-helpers (b2s_hip.ragged) and the opt-in switches (choice, rebind).  Nothing here needs a GPU."""
+"""CPU-only tests of what the bindings share: the loader (b2s_hip.cbind.Library), the workspace and pointer helpers, the status words
+and their raiser, the ragged-batch helpers (b2s_hip.ragged) and the opt-in switches (choice, rebind).  Nothing here needs a GPU."""
 import ctypes as C
 import sys
 import types
@@ -21,9 +21,10 @@ def test_missing_library_raises_the_documented_text(tmp_path):
 
 
 def test_the_four_libraries_keep_their_module_level_names():
-    from b2s_hip import B2SError, cbind, lib, mcd, metrics, vocoder
+    from b2s_hip import B2SError, cbind, durations, f0, lib, mcd, metrics, vocoder
     assert lib.B2SError is cbind.B2SError is B2SError
-    for mod, name in ((lib, "libb2s_hip.so"), (vocoder, "libb2s_vocoder.so"), (metrics, "libb2s_metrics.so"), (mcd, "libb2s_mcd.so")):
+    for mod, name in ((lib, "libb2s_hip.so"), (vocoder, "libb2s_vocoder.so"), (metrics, "libb2s_metrics.so"), (mcd, "libb2s_mcd.so"),
+                      (f0, "libb2s_f0.so"), (durations, "libb2s_dur.so")):
         assert mod.LIB_PATH == mod._LIB.path and mod.LIB_PATH.endswith(name)
         assert mod.EXPORTS == mod._LIB.exports == sorted(mod._PROTOS) and mod._LIB.protos is mod._PROTOS
         assert mod.load() is mod.load()                                # cached
@@ -68,6 +69,71 @@ def test_dptr_maps_none_and_on_request_empty_tensors_to_null():
     assert dptr(None) is None and dptr(None, empty_null=True) is None
     assert dptr(t).value == t.data_ptr() == dptr(t, empty_null=True).value
     assert dptr(empty, empty_null=True) is None and isinstance(dptr(empty), C.c_void_p)
+
+
+def test_nptr_is_null_for_none_and_for_a_tensor_without_elements():
+    from b2s_hip.cbind import nptr
+    t = torch.zeros(3)
+    assert nptr(None) is None and nptr(torch.zeros(0)) is None and nptr(torch.zeros(0, 4)) is None
+    assert isinstance(nptr(t), C.c_void_p) and nptr(t).value == t.data_ptr() and nptr(t[1:]).value == t.data_ptr() + 4
+
+
+def test_the_status_words_are_defined_once_and_shared():
+    from b2s_hip import cbind, durations, f0, mcd, metrics
+    assert (cbind.OK, cbind.EMPTY, cbind.FAILED) == (0, 1, 2)
+    for mod in (metrics, mcd, f0, durations):
+        assert (mod.OK, mod.EMPTY, mod.FAILED) == (0, 1, 2)
+    assert durations.SHORT == 3 and durations.STATUS_NAMES == ("OK", "EMPTY", "FAILED", "SHORT")
+
+
+def test_raise_failed_names_the_failed_items_in_each_of_the_three_texts():
+    from b2s_hip.cbind import EMPTY, FAILED, OK, B2SError, raise_failed
+    status = np.array([OK, FAILED, EMPTY, FAILED], np.int32)
+    for args, kwargs, want in (
+            (("DTW",), {}, "DTW failed for pairs [1, 3] (offsets inconsistent with the sizes)"),
+            (("MCD after DTW", "utterances"), {}, "MCD after DTW failed for utterances [1, 3] (offsets inconsistent with the sizes)"),
+            (("F0 after DTW",), {"why": "a non-finite sample, or sizes that do not fit together"},
+             "F0 after DTW failed for pairs [1, 3] (a non-finite sample, or sizes that do not fit together)")):
+        for st in (status, torch.from_numpy(status), status.tolist()):
+            with pytest.raises(B2SError) as e:
+                raise_failed(st, *args, **kwargs)
+            assert str(e.value) == want
+    for quiet in (np.array([OK, EMPTY, 3], np.int32), torch.tensor([OK, EMPTY], dtype=torch.int32), np.zeros(0, np.int32)):
+        assert raise_failed(quiet, "DTW") is None
+
+
+def test_default_hp_is_the_given_object_or_the_global_one():
+    import hyperparams
+    from b2s_hip.cbind import default_hp
+    hp = types.SimpleNamespace()
+    assert default_hp(hp) is hp and default_hp() is hyperparams.hparams and default_hp(None) is hyperparams.hparams
+
+
+def test_ragged_as_tensor_detaches_a_tensor_and_wraps_anything_else():
+    from b2s_hip import ragged
+    w = torch.ones(3, requires_grad=True) * 2.0
+    t = ragged.as_tensor(w)
+    assert w.requires_grad and not t.requires_grad and t.data_ptr() == w.data_ptr()
+    a = np.arange(6, dtype=np.int16).reshape(2, 3)
+    t = ragged.as_tensor(a)
+    assert t.dtype == torch.int16 and t.tolist() == a.tolist()
+    a[0, 0] = 7
+    assert t[0, 0] == 7                                                # the array's memory, not a copy
+    assert ragged.as_tensor([1.5, 2.5]).dtype == torch.float64 and ragged.as_tensor([[1, 2]]).shape == (1, 2)
+
+
+def test_ragged_lengths_i32():
+    from b2s_hip import B2SError, ragged
+    for given, want in (([3, 0, 7], [3, 0, 7]), (torch.tensor([3, 0, 7], dtype=torch.int64), [3, 0, 7]),
+                        (np.array([[3], [0], [7]]), [3, 0, 7]),                                    # any shape of B values
+                        (np.array([2.9, -1.9, 7.0]), [2, -1, 7]), (torch.tensor([2.9, -1.9, 7.0]), [2, -1, 7]),
+                        ([1000000, -5, 0], [1000000, -5, 0])):                                     # nothing is clamped
+        t = ragged.lengths_i32(given, 3, "cpu", "input_lengths")
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.tolist() == want
+    assert ragged.lengths_i32([], 0, "cpu", "dec_lengths").shape == (0,)
+    for given in ([3, 0], torch.tensor([3, 0]), np.array([3.0, 0.0])):
+        with pytest.raises(B2SError, match="^2 dec_lengths for a batch of 3$"):
+            ragged.lengths_i32(given, 3, "cpu", "dec_lengths")
 
 
 def test_ragged_offsets():

@@ -502,7 +502,7 @@ def test_f0_after_dtw_end_to_end_against_the_oracle_on_the_returned_pcm_and_path
 
 
 def test_command_line_rescoring_of_a_finished_eval(tmp_path, capsys):
-    from b2s_hip import f0, mcd
+    from b2s_hip import f0, rescore
     hp = hp_of()
     rng = np.random.default_rng(5)
     names = ["spk1_%02d" % i for i in range(6)]
@@ -536,8 +536,8 @@ def test_command_line_rescoring_of_a_finished_eval(tmp_path, capsys):
     # the same pairs in the same batches of 4 through the list function (checked against the oracle above)
     want = []
     for part in (slice(0, 4), slice(4, 6)):
-        preds, pl = mcd._pad(gen[part], names[part], 80, "generated")
-        targets, tl = mcd._pad(truth[part], names[part], 80, "target")
+        preds, pl = rescore.pad(gen[part], names[part], 80, "generated")
+        targets, tl = rescore.pad(truth[part], names[part], 80, "target")
         want += f0.calculate_f0_dtw(preds, pl, targets, tl, n_iter=4, hp=hp, threshold=0.3, silence_db=-60.0)
     for n, l, w in zip(names, langs, want):
         r = recs[n]
