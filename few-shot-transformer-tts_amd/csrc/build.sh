@@ -1,6 +1,6 @@
 #!/bin/bash
-# Build libb2s_hip.so and the five satellite libraries (libb2s_vocoder.so, libb2s_metrics.so, libb2s_mcd.so, libb2s_f0.so, libb2s_dur.so) for gfx950
-# (MI355X).  hipcc cross-compiles without a GPU.
+# Build libb2s_hip.so and the six satellite libraries (libb2s_vocoder.so, libb2s_metrics.so, libb2s_mcd.so, libb2s_f0.so, libb2s_dur.so,
+# libb2s_pros.so) for gfx950 (MI355X).  hipcc cross-compiles without a GPU.
 #   build.sh            only what changed
 #   build.sh --clean    recompile every source (what __graft_entry__.build() runs)
 #   build.sh --lab      measurement build with -DB2S_LAB (B2S_LAB_* environment switches that change results: skip the encoder, drop the
@@ -50,4 +50,7 @@ if [ "$1" != "--lab" ]; then
   satellite f0 "-ffp-contract=off" f0/f0.hip
   # monotonic alignment search and the duration error (include/b2s_dur.h); contraction off, every cell is one fp64 add and one compare
   satellite dur "-ffp-contract=off" dur/dur.hip
+  # prosody targets: window energy, Viterbi pitch track, sums per input unit (include/b2s_pros.h); contraction off, every product is
+  # rounded before it is added
+  satellite pros "-ffp-contract=off" pros/pros.hip
 fi
