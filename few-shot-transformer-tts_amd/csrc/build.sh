@@ -1,6 +1,6 @@
 #!/bin/bash
-# Build libb2s_hip.so and the seven satellite libraries (libb2s_vocoder.so, libb2s_metrics.so, libb2s_mcd.so, libb2s_f0.so, libb2s_dur.so,
-# libb2s_pros.so, libb2s_va.so) for gfx950 (MI355X).  hipcc cross-compiles without a GPU.
+# Build libb2s_hip.so and the eight satellite libraries (libb2s_vocoder.so, libb2s_metrics.so, libb2s_mcd.so, libb2s_f0.so, libb2s_dur.so,
+# libb2s_pros.so, libb2s_va.so, libb2s_vp.so) for gfx950 (MI355X).  hipcc cross-compiles without a GPU.
 #   build.sh            only what changed
 #   build.sh --clean    recompile every source (what __graft_entry__.build() runs)
 #   build.sh --lab      measurement build with -DB2S_LAB (B2S_LAB_* environment switches that change results: skip the encoder, drop the
@@ -56,4 +56,7 @@ if [ "$1" != "--lab" ]; then
   # the student's variance adaptor, forward and backward: quantise, embed, expand (include/b2s_va.h); contraction off with the
   # siblings, every sum is one rounded fp32 add after the other
   satellite va "-ffp-contract=off" va/va.hip
+  # the student's variance predictors, forward and backward: conv, ReLU, LayerNorm, dropout twice, Linear (include/b2s_vp.h);
+  # contraction off, every product outside an explicit fmaf is rounded before it is added
+  satellite vp "-ffp-contract=off" vp/vp.hip
 fi

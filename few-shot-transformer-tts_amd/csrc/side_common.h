@@ -1,5 +1,5 @@
 // The error core of a satellite library (libb2s_vocoder.so, libb2s_metrics.so, libb2s_mcd.so, libb2s_f0.so, libb2s_dur.so,
-// libb2s_pros.so, libb2s_va.so).  side_common.hip is compiled into each of them (build.sh), so each has a thread-local message slot of its own behind its b2s_*_last_error(); everything here has
+// libb2s_pros.so, libb2s_va.so, libb2s_vp.so).  side_common.hip is compiled into each of them (build.sh), so each has a thread-local message slot of its own behind its b2s_*_last_error(); everything here has
 // hidden visibility and stays out of the dynamic symbol tables.
 #pragma once
 #include <cstddef>
